@@ -17,7 +17,13 @@ one forward over one batch already resident in HBM. N GPUs = N processes (torchr
 sharded per rank with no data-path collective (weak scaling); each step ends with an RCCL
 all-gather of the per-pair poses.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0 (contract in the task statement). A plain run sets up, warms
+up, times ``--steps`` steps and prints the headline fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config). ``--dump-outputs DIR`` also writes what the
+last timed step returned as DIR/<name>.npy (dump_outputs); inputs and weights are seeded, so
+the same arguments give the same inputs in every run and build. ``--full`` adds the side
+legs, each a run of its own after the timed region, and their entries in the line:
+  sequential, eager:   the same steps without the pipeline / without the HIP-graph cache;
   roofline:            the KPConv gather kernel (the north star's HBM target): algorithmic
                        bytes per launch / average launch time from HIP events recorded by
                        libfgreg itself around its kernels inside the timed region;
@@ -31,7 +37,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                        fp32-equivalent product for f16x3), the fp32-MFMA figure as a note;
   cpu_baseline:        the CPU restatement (oracle/model_oracle.py, kind "port") timed on the
                        host cores on a bounded sample of the same workload (rank 0, N = 1).
-``--profile``: warmup + timed steps only (no counting, instrumented, tail or CPU legs), for
+``--profile``: a plain run (also under ``--full``) with marker kernels around the timed steps, for
 ``rocprofv3 --kernel-trace --stats`` runs whose per-step kernel sums must stay within
 ms_per_step (tools/kernel_stats.py).
 """
@@ -130,6 +136,12 @@ def parse():
                         'preprocesses step i + 1 on a side stream while step i\'s core runs)')
     p.add_argument('--profile', action='store_true',
                    help='warmup + timed steps only (for rocprofv3 kernel-trace runs)')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also run the side legs (sequential and eager '
+                        'timings, per-family rooflines, test-step tail, CPU baseline) and report '
+                        'them in the result line; a plain run times the steps only')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='write the outputs of the last timed step to DIR/<name>.npy (float32)')
     p.add_argument('--train', action='store_true',
                    help='time training steps instead (SURVEY §8(f) row 4): train() forward + '
                         'backward + clip_grad_norm_ + AdamW step; a side line, not the headline')
@@ -275,7 +287,13 @@ def main():
     if args.train:
         if args.gpus != 1:
             raise SystemExit('--train runs on one GPU')
+        if args.dump_outputs:
+            raise SystemExit('--dump-outputs writes the forward benchmark\'s outputs, not --train\'s')
         return train_main(args)
+    # a plain run: set up, warm up, time the steps, print the line; every side leg is --full's
+    lean = args.profile or not args.full
+    if (args.gemm_table or args.gather_table) and lean:
+        raise SystemExit('--gemm-table / --gather-table come from the instrumented replay: add --full')
     import fgreg
     from fgreg import linear as lin
     from fgreg import ops
@@ -338,24 +356,34 @@ def main():
     def run(n):
         """n full forwards of the batch: pipelined (fgreg.pipeline: step i + 1's
         preprocessing on a side stream during step i's core) unless --no-pipeline"""
+        out = None
         if args.no_pipeline:
             for _ in range(n):
-                step()
-            return
+                out = step()
+            return out
         batches = ({'src_xyz': batch_src, 'tgt_xyz': batch_tgt} for _ in range(n))
         for out in fgreg.pipeline(model, batches):
             finish(out)
+        return out
 
     def timed(n):
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(n)
+        last[0] = run(n)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         return time.perf_counter() - t0
+
+    last = [None]                 # what the latest timed(n)'s final step returned
+
+    def dump():
+        """--dump-outputs: the final timed step's outputs, before anything else runs"""
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last[0], rank, world)
+        last[0] = None
 
     from fgreg import regtr as fregtr
     fpipe = sys.modules['fgreg.pipeline']            # the module (fgreg.pipeline is the function)
@@ -370,6 +398,10 @@ def main():
             elapsed = timed(args.steps)
             torch.cuda._sleep(1000)
             torch.cuda.synchronize()
+            dump()
+        elif lean:
+            elapsed = timed(args.steps)
+            dump()
         else:
             # algorithmic work per launch (untimed pass with counting on)
             fams = ['kpconv_gather', 'attention', 'gemm', 'res2net'] + list(OTHER)
@@ -382,6 +414,7 @@ def main():
             ops.TIMER = None
             # timed region: nothing instrumented (graph replay of the core forward)
             elapsed = timed(args.steps)
+            dump()
             # one forward at a time (back-to-back model(batch), graph replay): the latency of
             # a step, reported beside the pipelined throughput
             elapsed_seq = None
@@ -416,7 +449,7 @@ def main():
             tail_ms, tail_inputs = test_tail(model, batch_src, batch_tgt, src, tgt, pose_gt, dev,
                                               args.steps)
 
-    el = torch.tensor([elapsed, elapsed_eager if not args.profile else 0.0], dtype=torch.float64,
+    el = torch.tensor([elapsed, elapsed_eager if not lean else 0.0], dtype=torch.float64,
                       device=dev if backend == 'nccl' else 'cpu')
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -443,20 +476,21 @@ def main():
                                 f'consecutive cores alternate over {fpipe.STREAMS} core streams '
                                 '(one HIP-graph instance each), so their launches overlap')},
     }
-    if not args.profile and elapsed_seq is not None:
+    if not lean and elapsed_seq is not None:
         line['sequential'] = {
             'value': n_total * args.steps / elapsed_seq, 'unit': 'pairs/s',
             'ms_per_step': elapsed_seq / args.steps * 1e3,
             'what': 'the same steps one forward at a time (back-to-back model(batch), graph '
                     'replay, no overlap of consecutive forwards): the per-batch latency'}
-    if not args.profile:
+    if not lean:
         line['eager'] = {
             'value': n_total * args.steps / elapsed_eager, 'unit': 'pairs/s',
             'ms_per_step': elapsed_eager / args.steps * 1e3,
             'what': 'the same timed steps with the HIP-graph cache off (FGREG_GRAPHS=0: every '
                     'launch eager), i.e. inputs whose shape signature never repeats'}
-    if args.profile:
-        line['profile'] = 'warmup + timed steps only (rocprofv3 companion run)'
+    if lean:
+        if args.profile:
+            line['profile'] = 'warmup + timed steps only (rocprofv3 companion run)'
         if rank == 0:
             print(json.dumps(line), flush=True)
         if dist is not None:
@@ -546,6 +580,43 @@ def main():
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: all files of a run together stay below this
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: what the final timed step returned to its caller, one float32 .npy per
+    tensor: <key>.npy for a tensor entry of the output dict (pose, and pose_all at N > 1),
+    <key>.<pair>.npy for each per-pair entry of a list (features, keypoints, warped keypoints,
+    overlap logits). Ranks above 0 prefix their files with rank<r>. (each rank holds its own
+    pairs). Arrays are written whole while everything fits DUMP_BYTES (shared evenly between
+    ranks); otherwise each is flattened and thinned to the same fraction of its elements at
+    indices drawn from a fixed seed in sorted-name order, so two builds given the same
+    arguments write the same elements."""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v
+        elif isinstance(v, (list, tuple)):
+            for b, t in enumerate(v):
+                if torch.is_tensor(t):
+                    arrays[f'{k}.{b}'] = t
+    arrays = {k: t.detach().to(torch.float32).cpu().numpy() for k, t in sorted(arrays.items())}
+    budget = DUMP_BYTES // world - 256 * len(arrays)          # .npy headers
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        rng = np.random.default_rng(0)
+        frac = budget / total
+        for k, a in arrays.items():
+            if a.size == 0:
+                continue
+            keep = max(1, int(a.size * frac))
+            arrays[k] = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    prefix = f'rank{rank}.' if rank else ''
+    for k, a in arrays.items():
+        np.save(os.path.join(path, prefix + k + '.npy'), np.ascontiguousarray(a))
 
 
 def write_gather_table(path, rtimer, work, steps, step_ms):

@@ -5,6 +5,7 @@ HIP path through the C ABI (libfgreg.so). The oracle (oracle/) is only ever used
 here as the checker.
 """
 import ast
+import glob
 import os
 import sys
 
@@ -25,8 +26,23 @@ def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs an AMD MI355X GPU (HIP path through libfgreg.so)')
 
 
+class _Parts:
+    """A fixture that make_golden.save wrote as <name>.npz + <name>.part<k>.npz (every committed
+    file stays under 1 MiB), read as the one archive it is: .files and [key]."""
+
+    def __init__(self, parts):
+        self._of = {k: p for p in parts for k in p.files}
+        self.files = list(self._of)
+
+    def __getitem__(self, key):
+        return self._of[key][key]
+
+
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False)
+    paths = [os.path.join(GOLDEN, name + '.npz')] + sorted(
+        glob.glob(os.path.join(GOLDEN, glob.escape(name) + '.part*.npz')))
+    parts = [np.load(p, allow_pickle=False) for p in paths]
+    return parts[0] if len(parts) == 1 else _Parts(parts)
 
 
 def forward_fixture(name):

@@ -3,23 +3,20 @@
 * mat2quat: known answers (axis-angle rotations, identity, w >= 0 sign convention);
 * est.log writer -> Redwood reader round trip (generic_reg_model.py:265-286 format);
 * the benchmark on synthetic gt.log / gt.info scenes, against hand-counted recall;
-* where the reference is mounted (this container only): evaluate_registration and
-  benchmark of benchmark/benchmark_predator.py run on the same files, with nibabel (absent
-  here) stubbed by fgreg's mat2quat -- this pins the parsing / masking / recall logic, not
-  the quaternion (that is pinned by the known answers).
+* the recorded results of evaluate_registration and benchmark of the reference's
+  benchmark/benchmark_predator.py on the same files (tests/golden/rr3dmatch_reference.npz),
+  made with nibabel stubbed by fgreg's mat2quat -- this pins the parsing / masking / recall
+  logic, not the quaternion (that is pinned by the known answers).
 """
 import math
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
+from conftest import golden
 from fgreg import rr3dmatch as rr
-
-REF = '/root/reference'
 
 
 def _rot(axis, ang):
@@ -127,30 +124,26 @@ def test_benchmark_recall(tmp_path):
     assert os.path.exists(os.path.join(est_root, per['scene'][0], 'flag.npy'))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'benchmark')),
-                    reason='reference checkout not mounted (GPU box)')
-def test_benchmark_matches_reference(tmp_path, monkeypatch):
-    nib = types.ModuleType('nibabel')
-    nq = types.ModuleType('nibabel.quaternions')
-    nq.mat2quat = rr.mat2quat
-    nib.quaternions = nq
-    monkeypatch.setitem(sys.modules, 'nibabel', nib)
-    monkeypatch.setitem(sys.modules, 'nibabel.quaternions', nq)
-    monkeypatch.syspath_prepend(os.path.join(REF, 'benchmark'))
-    monkeypatch.setenv('PYTHONDONTWRITEBYTECODE', '1')
-    sys.dont_write_bytecode = True
-    import importlib
-    bp = importlib.import_module('benchmark_predator')
-    gt_root, est_root, _ = _make_benchmark(tmp_path, seed=3)
-    for scene in sorted(os.listdir(gt_root)):
+REFERENCE_SEED = 3      # the scenes tests/golden/rr3dmatch_reference.npz was recorded on
+
+
+def test_benchmark_matches_reference(tmp_path):
+    """Against the results of the reference's own evaluate_registration / benchmark
+    (benchmark/benchmark_predator.py) on the same files, recorded by tests/golden/make_golden.py
+    rr3dmatch (inputs read there by the reference's readers, here by fgreg's)."""
+    ref = golden('rr3dmatch_reference')
+    gt_root, est_root, _ = _make_benchmark(tmp_path, seed=REFERENCE_SEED)
+    scenes = sorted(os.listdir(gt_root))
+    assert sorted(k[:-2] for k in ref.files if k.endswith('.0')) == scenes
+    for scene in scenes:
         g = os.path.join(gt_root, scene)
-        gp, gtr = bp.read_trajectory(os.path.join(g, 'gt.log'))
-        n, info = bp.read_trajectory_info(os.path.join(g, 'gt.info'))
-        ep, etr = bp.read_trajectory(os.path.join(est_root, scene, 'est.log'))
-        want = bp.evaluate_registration(n, etr, ep, gp, gtr, info)
+        gp, gtr = rr.read_trajectory(os.path.join(g, 'gt.log'))
+        n, info = rr.read_trajectory_info(os.path.join(g, 'gt.info'))
+        ep, etr = rr.read_trajectory(os.path.join(est_root, scene, 'est.log'))
+        want = [ref[f'{scene}.{j}'] for j in range(4)]
         got = rr.evaluate_registration(n, etr, ep, gp, gtr, info)
-        assert got[0] == want[0] and got[1] == want[1] and list(got[2]) == list(want[2])
+        assert got[0] == float(want[0]) and got[1] == float(want[1])
+        assert list(got[2]) == list(want[2])
         np.testing.assert_allclose(got[3], want[3], rtol=1e-12, equal_nan=True)
-    _, want_recall = bp.benchmark(est_root, gt_root)
     _, got_recall, _ = rr.benchmark(est_root, gt_root)
-    assert got_recall == pytest.approx(want_recall, abs=1e-15)
+    assert got_recall == pytest.approx(float(ref['mean_recall']), abs=1e-15)

@@ -1,21 +1,17 @@
 """Input side of the test step (fgreg.transforms).
 
-Where the reference is mounted (this container), the ModelNet crop test pipeline is run
-through the reference's own transform objects (data_loaders/modelnet_transforms.py, in the
-order of data_loaders/modelnet.py:111-117) on the same raw clouds and sample indices, and
-every output field must match exactly. Elsewhere only the shape / invariant checks run.
+The ModelNet crop test pipeline must match, field for field and exactly, what the reference's
+own transform objects (data_loaders/modelnet_transforms.py, in the order of
+data_loaders/modelnet.py:111-117) gave on the same raw clouds and sample indices
+(tests/golden/modelnet_crop_reference.npz, recorded by tests/golden/make_golden.py crop).
 """
-import os
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+from conftest import golden
 from fgreg import transforms as T
 from fgreg.synthetic import _box_surface
-
-REF = '/root/reference'
 
 
 def _raw(i, normals=False):
@@ -56,33 +52,23 @@ def test_collate_pair():
     assert b2['overlap_p'].shape == (1,) and b2['src_path'] == ['a']
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'data_loaders')),
-                    reason='reference checkout not mounted (GPU box)')
-@pytest.mark.parametrize('i,normals', [(0, False), (5, False), (42, True)])
-def test_crop_pipeline_matches_reference(i, normals, monkeypatch):
-    monkeypatch.syspath_prepend(REF)
-    sys.dont_write_bytecode = True
-    import importlib.util
-    # the file alone: data_loaders/__init__ pulls in h5py / torchvision (absent here)
-    spec = importlib.util.spec_from_file_location(
-        'ref_modelnet_transforms', os.path.join(REF, 'data_loaders', 'modelnet_transforms.py'))
-    mt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mt)
-    steps = [mt.SetDeterministic(), mt.SplitSourceRef(), mt.RandomCrop([0.7, 0.7]),
-             mt.RandomTransformSE3_euler(rot_mag=45.0, trans_mag=0.5), mt.Resampler(1024),
-             mt.RandomJitter(), mt.ShufflePoints()]
-    raw = _raw(i, normals)
-    sample = {'points': raw.copy(), 'label': 0, 'idx': np.array(i, dtype=np.int32)}
-    for st in steps:
-        sample = st(sample)
-    got = T.modelnet_crop_test(raw.copy(), i)
-    np.testing.assert_array_equal(got['src_xyz'].numpy(), sample['points_src'][:, :3])
-    np.testing.assert_array_equal(got['tgt_xyz'].numpy(), sample['points_ref'][:, :3])
-    np.testing.assert_array_equal(got['tgt_raw'].numpy(), sample['points_raw'][:, :3])
-    np.testing.assert_array_equal(got['pose'].numpy(), sample['transform_gt'])
-    np.testing.assert_array_equal(got['correspondences'].numpy(), sample['correspondences'])
-    np.testing.assert_array_equal(got['src_overlap'].numpy(), sample['src_overlap'])
-    np.testing.assert_array_equal(got['tgt_overlap'].numpy(), sample['ref_overlap'])
+CROP_CASES = [(0, False), (5, False), (42, True)]
+# our field -> the reference sample's field (tests/golden/modelnet_crop_reference.npz holds the
+# latter, recorded from the reference's own transform objects by make_golden.make_crop_reference)
+CROP_FIELDS = {'src_xyz': 'points_src', 'tgt_xyz': 'points_ref', 'tgt_raw': 'points_raw',
+               'pose': 'transform_gt', 'correspondences': 'correspondences',
+               'src_overlap': 'src_overlap', 'tgt_overlap': 'ref_overlap'}
+
+
+@pytest.mark.parametrize('i,normals', CROP_CASES)
+def test_crop_pipeline_matches_reference(i, normals):
+    ref = golden('modelnet_crop_reference')
+    got = T.modelnet_crop_test(_raw(i, normals), i)
+    for ours, theirs in CROP_FIELDS.items():
+        want = ref[f'{i}.{theirs}']
+        if ours in ('src_xyz', 'tgt_xyz', 'tgt_raw'):
+            want = want[:, :3]
+        np.testing.assert_array_equal(got[ours].numpy(), want, err_msg=ours)
 
 
 @pytest.mark.parametrize('n', [2, 1100, 2048, 4096])

@@ -1,4 +1,5 @@
-"""Prints the key numbers of one or more bench JSON lines (gpurun_out/*.json)."""
+"""Prints the key numbers of one or more bench JSON lines (the roofline and CPU entries are
+there when the line came from ``bench.py --full``)."""
 import json
 import sys
 

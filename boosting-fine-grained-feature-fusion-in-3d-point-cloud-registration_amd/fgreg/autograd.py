@@ -48,7 +48,7 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty((c,), dtype=torch.float32, device=x.device)
     L = _lib.load()
     nb = _lib.ws_size('fgr_colsum_workspace', n, c)
-    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    ws = ops.scratch(x.device, nb)
     _lib.check(L.fgr_colsum(_ptr(x), n, c, max(x.stride(0), c), _ptr(out), _ptr(ws), nb,
                             _stream()), 'fgr_colsum')
     return out
@@ -166,7 +166,7 @@ def nbr_inverse(idx: torch.Tensor, ns: int):
     L = _lib.load()
     nb = _lib._sz(0)
     _lib.check(L.fgr_nbr_inverse_workspace(nq, width, ns, nb), 'fgr_nbr_inverse_workspace')
-    ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
+    ws = ops.scratch(dev, max(nb.value, 1))
     _lib.check(L.fgr_nbr_inverse(_ptr(idx), nq, width, ns, _ptr(start), _ptr(pos), _ptr(ent),
                                  _ptr(ws), nb.value, _stream()), 'fgr_nbr_inverse')
     res = (start, pos, ent)
@@ -245,7 +245,7 @@ class _MaxPoolFn(torch.autograd.Function):
         L = _lib.load()
         nb = _lib._sz(0)
         _lib.check(L.fgr_max_pool_bwd_workspace(nq, c, nb), 'fgr_max_pool_bwd_workspace')
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device)
+        ws = ops.scratch(x.device, nb.value)
         _lib.check(L.fgr_max_pool_bwd(_ptr(x), ns, c, _ptr(idx.contiguous()), nq, width, _ptr(dy),
                                       _ptr(start), _ptr(ent), _ptr(dx), _ptr(ws), nb.value,
                                       _stream()), 'fgr_max_pool_bwd')
@@ -261,7 +261,7 @@ def max_pool_t(x, idx):
 # ------------------------------------------------------------------------------------------
 def _seg_ws(max_len, c, n_seg, extra=0, device=None):
     nb = _lib.ws_size('fgr_segnorm_workspace', max_len, c, n_seg)
-    return torch.empty(nb + extra, dtype=torch.uint8, device=device)
+    return ops.scratch(device, nb + extra)
 
 
 class _SegNormFn(torch.autograd.Function):
@@ -362,7 +362,7 @@ class _LayerNormFn(torch.autograd.Function):
         L = _lib.load()
         nb = _lib._sz(0)
         _lib.check(L.fgr_layernorm_bwd_workspace(n, d, nb), 'fgr_layernorm_bwd_workspace')
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device)
+        ws = ops.scratch(x.device, nb.value)
         _lib.check(L.fgr_layernorm_bwd(_ptr(x), n, d, _ptr(gamma.contiguous()), ctx.eps, _ptr(dy),
                                        _ptr(dx), _ptr(dgb), _ptr(ws), nb.value, _stream()),
                    'fgr_layernorm_bwd')
@@ -476,7 +476,7 @@ class _CorrAttentionFn(torch.autograd.Function):
         L = _lib.load()
         nb = _lib._sz(0)
         _lib.check(L.fgr_corr_attention_bwd_workspace(n, nb), 'fgr_corr_attention_bwd_workspace')
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=q.device)
+        ws = ops.scratch(q.device, nb.value)
         n_seg = q_off.numel() - 1
         _lib.check(L.fgr_corr_attention_bwd(
             _ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(_c(xyz, torch.float32)), _ptr(dcorr),

@@ -65,7 +65,7 @@ class _Image:
         L = _lib.load()
         fn = self.FN[mode]
         nb = _lib.ws_size(fn + '_bytes', n, k)
-        self.img = torch.empty(nb, dtype=torch.uint8, device=w2.device)
+        self.img = ops.scratch(w2.device, nb)
         _lib.check(getattr(L, fn)(_ptr(w2), n, k, sn, sk, _ptr(self.img), _stream()), fn)
         self.n, self.k, self.sn, self.sk, self.mode = n, k, sn, sk, mode
         self.src, self.version, self.ptr = src, src._version, src.data_ptr()

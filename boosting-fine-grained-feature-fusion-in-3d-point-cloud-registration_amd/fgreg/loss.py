@@ -149,7 +149,7 @@ def circle(anchor_feat, positive_feat, anchor_xyz, positive_xyz, a_lens, p_lens,
     L = _lib.load()
     nb = _lib._sz(0)
     _lib.check(L.fgr_circle_loss_workspace(fd_elems, n_a, n_p, nb), 'fgr_circle_loss_workspace')
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=A.device)
+    ws = ops.scratch(A.device, nb.value)
     out = torch.empty((), dtype=torch.float32, device=A.device)
     axyz, pxyz = _c(anchor_xyz, torch.float32), _c(positive_xyz, torch.float32)
     _lib.check(L.fgr_circle_loss(_ptr(A), _ptr(P), A.shape[1], _ptr(axyz), _ptr(pxyz),

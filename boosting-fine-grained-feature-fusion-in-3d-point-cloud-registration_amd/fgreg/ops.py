@@ -228,7 +228,7 @@ def grid_subsample(points: torch.Tensor, off: torch.Tensor, lengths: Sequence[in
         ws_bytes = _lib._sz(0)
         _lib.check(L.fgr_grid_subsample_workspace(n, nc, cap, ws_bytes),
                    'fgr_grid_subsample_workspace')
-        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=pts.device)
+        ws = scratch(pts.device, ws_bytes.value)
         t0 = _begin('grid_subsample')
         _lib.check(L.fgr_grid_subsample_count(_ptr(pts), _ptr(off), nc, n, float(dl), cap,
                                               _ptr(ws), ws_bytes.value, _ptr(counts), st),
@@ -290,7 +290,7 @@ class RadiusGrid:
         L = _lib.load()
         nb = _lib._sz(0)
         _lib.check(L.fgr_radius_grid_workspace(self.s.shape[0], nc, nb), 'fgr_radius_grid_workspace')
-        self.ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=s.device)
+        self.ws = scratch(s.device, max(nb.value, 1))
         self.nbytes = nb.value
         t0 = _begin('radius_search')
         _lib.check(L.fgr_radius_grid_build(_ptr(self.s), _ptr(s_off), nc, self.s.shape[0],
@@ -453,7 +453,7 @@ def instnorm(x, seg_off, lengths, row_div=None, act=ACT_NONE, residual=None, pos
     L = _lib.load()
     nb = _lib._sz(0)
     _lib.check(L.fgr_instnorm_workspace(max_len, c, n_seg, nb), 'fgr_instnorm_workspace')
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
+    ws = scratch(x.device, nb.value) if nb.value else None
     t0 = _begin('instnorm')
     _lib.check(L.fgr_instnorm(_ptr(x), n, c, _ptr(seg_off), n_seg, max_len, _ptr(row_div),
                               float(eps), act, _ptr(residual), post_act, _ptr(out), _ptr(ws),
@@ -759,6 +759,13 @@ class PrivateWorkspace:
         return False
 
 
+def scratch(device, nbytes):
+    """A fresh buffer of exactly ``nbytes`` from the caching allocator: the scratch of the call
+    sites that size one per call (and the weight images). One function, so that a test can
+    swap the provider for guarded exact-size views (tests/test_gpu_footprint.py)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def _workspace(device, nbytes):
     """Grow-only scratch buffer per device, reused by consecutive launches on the current
     stream (stream order serialises the reuse). Outgrown buffers are kept alive: a captured
@@ -953,7 +960,7 @@ def corr_topk_mask(corr, q, k, q_off, kv_off, kv_seg, n_clouds, max_q_len, max_k
     L = _lib.load()
     nb = _lib._sz(0)
     _lib.check(L.fgr_corr_topk_workspace(q.shape[0], max_kv_len, nb), 'fgr_corr_topk_workspace')
-    ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=q.device)
+    ws = scratch(q.device, max(nb.value, 1))
     _lib.check(L.fgr_corr_topk_mask(
         _ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(corr), _ptr(q_off), _ptr(kv_off),
         _ptr(kv_seg), q_off.numel() - 1, n_clouds, q.shape[0], int(max_q_len), int(max_kv_len), d,

@@ -900,6 +900,37 @@ def ffn(x, norm, w1_img, b1, w2_img, b2, bound, out=None) -> torch.Tensor:
     return out
 
 
+def pos_mlp_supported(n, d) -> bool:
+    """True if the learned positional embedding of n points to width d runs as one launch
+    (fgr_pos_mlp_f16x3: d = 256 or 512)."""
+    return bool(_lib.load().fgr_pos_mlp_f16x3_supported(int(n), int(d)))
+
+
+def pos_mlp(xyz, w0, b0, imgs, biases, out=None) -> torch.Tensor:
+    """PositionEmbeddingLearned's five-layer MLP (position_embedding.py:52-71) on xyz (n, 3) in
+    one launch: w0 / b0 = mlp[0]'s raw weight (32, 3) and bias, imgs = the four
+    linear.weight_image(mlp[2 i].weight, mode='f16x3') of layers 1-4, biases their four
+    biases. ``out`` (n, d) may be a row-strided view (stride % 4 == 0, 16-B aligned)."""
+    _dev(xyz, w0, b0, *biases)
+    xyz = _c(xyz, torch.float32)
+    n, d = xyz.shape[0], biases[3].numel()
+    assert xyz.dim() == 2 and xyz.shape[1] == 3 and len(imgs) == 4 and len(biases) == 4
+    w0, b0 = _c(w0, torch.float32), _c(b0, torch.float32)
+    assert w0.shape == (32, 3) and b0.numel() == 32
+    biases = [_c(b, torch.float32) for b in biases]
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.float32, device=xyz.device)
+    assert out.shape == (n, d) and out.dtype == torch.float32 and (n == 0 or out.stride(1) == 1)
+    t0 = _begin('gemm', ('pos_mlp', n, d))
+    _lib.check(_lib.load().fgr_pos_mlp_f16x3(
+        _ptr(xyz), n, _ptr(w0), _ptr(b0), _ptr(imgs[0].img), _ptr(biases[0]), _ptr(imgs[1].img),
+        _ptr(biases[1]), _ptr(imgs[2].img), _ptr(biases[2]), _ptr(imgs[3].img), _ptr(biases[3]),
+        d, _ptr(out), out.stride(0) if n > 1 else max(out.stride(0), d), _stream()),
+        'fgr_pos_mlp_f16x3')
+    _end('gemm', t0, 2 * n * (3 * 32 + 32 * 64 + 64 * 128 + 128 * 256 + 256 * d))
+    return out
+
+
 def corr_head_supported(m, d) -> bool:
     return bool(_lib.load().fgr_corr_head_supported(int(m), int(d)))
 

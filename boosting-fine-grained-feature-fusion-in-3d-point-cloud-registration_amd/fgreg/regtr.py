@@ -24,7 +24,7 @@ from . import linear as lin
 from . import ops
 from .linear import linear
 from .backbone import KPFEncoder, PreprocessorHIP, host_layout
-from .transformer import (PositionEmbeddingCoordsSine, Segments, TransformerCrossEncoder,
+from .transformer import (PositionEmbeddingCoordsSine, PositionEmbeddingLearned, Segments, TransformerCrossEncoder,
                           TransformerCrossEncoderLayer)
 
 _logger = logging.getLogger(__name__)
@@ -234,10 +234,16 @@ class RegTR(nn.Module):
         self.preprocessor = PreprocessorHIP(cfg, neighbor_mode=neighbor_mode)
         self.kpf_encoder = KPFEncoder(cfg, cfg.d_embed)
         self.feat_proj = nn.Linear(self.kpf_encoder.encoder_skip_dims[-1], cfg.d_embed, bias=True)
-        if cfg.get('pos_emb_type', 'sine') != 'sine':
-            raise NotImplementedError('pos_emb_type other than sine is not in the reference configs')
-        self.pos_embed = PositionEmbeddingCoordsSine(3, cfg.d_embed,
-                                                     scale=cfg.get('pos_emb_scaling', 1.0))
+        pos_emb_type = cfg.get('pos_emb_type', 'sine')
+        if pos_emb_type == 'sine':
+            self.pos_embed = PositionEmbeddingCoordsSine(3, cfg.d_embed,
+                                                         scale=cfg.get('pos_emb_scaling', 1.0))
+        elif pos_emb_type == 'learned':
+            # finegrained_regtr.py:45-49; the same module object goes to the CorrespondenceDecoder
+            # below, so a checkpoint carries the MLP under both prefixes (as the reference's)
+            self.pos_embed = PositionEmbeddingLearned(3, cfg.d_embed)
+        else:
+            raise NotImplementedError(f"pos_emb_type {pos_emb_type!r}: 'sine' or 'learned'")
         layer = TransformerCrossEncoderLayer(
             cfg.d_embed, cfg.nhead, cfg.d_feedforward, cfg.dropout,
             activation=cfg.transformer_act, normalize_before=cfg.pre_norm,

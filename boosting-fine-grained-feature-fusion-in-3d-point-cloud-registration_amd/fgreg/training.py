@@ -22,6 +22,7 @@ from .autograd import (attention_t, batchnorm_t, corr_attention_t, kpconv_t, lay
                        linear_t, max_pool_t, segnorm_t)
 from .backbone import ResnetBottleneckBlock, SimpleBlock, UnaryBlock, _level_inputs, host_layout
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
+from .transformer import PositionEmbeddingLearned
 
 
 def unary_train(u: UnaryBlock, x, off, lens, residual=None, post_act=ACT_NONE):
@@ -161,8 +162,11 @@ def core_train(model, meta, seg, B):
         x = block_train(block, x, meta)
     both = linear_t(x, model.feat_proj.weight, model.feat_proj.bias)
     xyz_c = meta['points'][-1]
-    with torch.no_grad():
-        pe = model.pos_embed(xyz_c)
+    if isinstance(model.pos_embed, PositionEmbeddingLearned):
+        pe = model.pos_embed.train_forward(xyz_c)       # gradients reach the MLP's parameters
+    else:
+        with torch.no_grad():
+            pe = model.pos_embed(xyz_c)
     pos = pe if cfg.transformer_encoder_has_pos_emb else None
     enc = model.transformer_encoder
     h = both

@@ -305,3 +305,61 @@ class PositionEmbeddingCoordsSine(nn.Module):
 
     def forward(self, xyz):
         return ops.sine_pos_embed(xyz, self.d_model, self.temperature, self.scale)
+
+
+class PositionEmbeddingLearned(nn.Module):
+    """position_embedding.py:52-71: the per-point MLP 3 -> 32 -> 64 -> 128 -> 256 -> d_model with
+    ReLU between the layers (``pos_emb_type: learned``). ``self.mlp`` has the reference's layout
+    (Linear at indices 0, 2, 4, 6, 8), so its state_dict keys are ``mlp.{0,2,4,6,8}.{weight,
+    bias}``.
+
+    Inference: one launch (ops.pos_mlp, fgr_pos_mlp_f16x3) where ops.pos_mlp_supported, else
+    five linear() calls. The MLP always runs in f16x3, in both precision modes -- like the sine
+    embedding, which is fp32 under lin.MODE == 'bf16' too: the embedding is added to every
+    attention input, and at 0.1 % of the forward's products it buys nothing in bf16. Training
+    (train_forward) goes through autograd.linear_t, so the ten parameters get gradients from
+    the existing backward kernels. Weight images come from the linear.weight_image cache: an
+    in-place update or load_state_dict invalidates them like every other layer's."""
+
+    def __init__(self, n_dim=3, d_model=256):
+        super().__init__()
+        if n_dim != 3:
+            raise NotImplementedError('coordinates are 3-D in this path')
+        self.n_dim, self.d_model = n_dim, d_model
+        self.mlp = nn.Sequential(
+            nn.Linear(n_dim, 32), nn.ReLU(),
+            nn.Linear(32, 64), nn.ReLU(),
+            nn.Linear(64, 128), nn.ReLU(),
+            nn.Linear(128, 256), nn.ReLU(),
+            nn.Linear(256, d_model))
+
+    def _linears(self):
+        return [self.mlp[i] for i in (0, 2, 4, 6, 8)]
+
+    def forward(self, xyz):
+        ls = self._linears()
+        with lin.mode_scope('f16x3'):
+            if ops.pos_mlp_supported(xyz.shape[0], self.d_model):
+                imgs = [lin.weight_image(m.weight, mode='f16x3') for m in ls[1:]]
+                return ops.pos_mlp(xyz, ls[0].weight, ls[0].bias, imgs, [m.bias for m in ls[1:]])
+            return self.forward_chain(xyz)
+
+    def forward_chain(self, xyz):
+        """The same MLP as five linear() launches (the path for widths the fused kernel refuses,
+        and its A/B baseline)."""
+        ls = self._linears()
+        h = xyz.contiguous()
+        with lin.mode_scope('f16x3'):
+            for i, m in enumerate(ls):
+                h = lin.linear(h, m.weight, m.bias, act=ops.ACT_RELU if i < 4 else ops.ACT_NONE)
+        return h
+
+    def train_forward(self, xyz):
+        """Differentiable forward: five autograd.linear_t calls (f16x3)."""
+        from .autograd import linear_t
+        ls = self._linears()
+        h = xyz.contiguous()
+        with lin.mode_scope('f16x3'):
+            for i, m in enumerate(ls):
+                h = linear_t(h, m.weight, m.bias, act=ops.ACT_RELU if i < 4 else ops.ACT_NONE)
+        return h

@@ -301,6 +301,27 @@ int fgr_ffn_f16x3(const float* x, int64_t ldx, const float* gamma, const float* 
                   const float* bound, float* out, int64_t ldo, int32_t m, int32_t d, int32_t f,
                   void* stream);
 
+/* PositionEmbeddingLearned (position_embedding.py:52-71) in one launch: the per-point MLP
+ *   out[r] = L4(ReLU(L3(ReLU(L2(ReLU(L1(ReLU(L0(xyz[r])))))))))
+ * with Linear widths 3 -> 32 -> 64 -> 128 -> 256 -> d_model (the hidden widths are the
+ * reference's and fixed). xyz (n, 3) contiguous fp32; out (n, d_model) with row stride ldo.
+ * Layer 0 (K = 3) runs in fp32 FMAs on the raw weight w0 (32, 3) row-major and bias b0 (32);
+ * layers 1-4 are the f16x3 products of fgr_gemm_f16x3: wL_img = fgr_split_weights_h3 of
+ * LinearL.weight ((64, 32), (128, 64), (256, 128), (d_model, 256); fgr_split_weights_h3_bytes
+ * bytes each), bL the raw fp32 bias. Each hidden row is scaled for its fp16 split by one power
+ * of two taken from that row's actual maximum (no host-supplied bound); the hidden activations
+ * never leave the chip. A row's result depends on that row's coordinates alone -- bit for bit,
+ * whatever the other rows of the call and wherever it stands in it. No workspace. Images, b1..b4
+ * and out 16-B aligned, ldo >= d_model, ldo % 4 == 0; out[r][d_model .. ldo) is not written.
+ * fgr_pos_mlp_f16x3_supported(n, d_model): n >= 1 and d_model 256 or 512; another d_model is
+ * FGR_E_ARG with a message; n = 0 returns FGR_OK and touches nothing (as fgr_sine_pos_embed).
+ * Replaces five fgr_gemm_f16x3 launches (FGR_ACT_RELU on the first four). */
+int fgr_pos_mlp_f16x3_supported(int64_t n, int32_t d_model);
+int fgr_pos_mlp_f16x3(const float* xyz, int64_t n, const float* w0, const float* b0,
+                      const void* w1_img, const float* b1, const void* w2_img, const float* b2,
+                      const void* w3_img, const float* b3, const void* w4_img, const float* b4,
+                      int32_t d_model, float* out, int64_t ldo, void* stream);
+
 int fgr_split_weights_bf16_bytes(int32_t n, int32_t k, size_t* bytes);
 int fgr_split_weights_bf16(const float* w, int32_t n, int32_t k, int64_t stride_n,
                            int64_t stride_k, void* img, void* stream);

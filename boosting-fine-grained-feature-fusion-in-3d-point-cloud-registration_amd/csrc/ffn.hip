@@ -1,7 +1,10 @@
 // The pre-norm transformer's position-wise feed-forward sub-layer in ONE launch
 // (transformers.py:231-238, forward_pre):
 //
-//   y = x + linear2(ReLU(linear1(LayerNorm3(x))))        x (M, d), d = 256, hidden F
+//   y = x + linear2(act(linear1(LayerNorm3(x))))         x (M, d), d = 256, hidden F
+//
+// act = ReLU (`transformer_act: relu`, both kernels below) or the exact erf GELU
+// (`transformer_act: gelu`, transformers.py:265-273; the weight-split kernel only).
 //
 // fp32-accurate f16x3 products (three fp16 MFMA term products per product, as gemm_rs.hip).
 //
@@ -34,6 +37,10 @@
 // {M1, Mb} from the host), so h S <= 2^15 with S = 2^e, bound S in [2^14, 2^15): no fp16
 // overflow. Values below the bound keep an ABSOLUTE split error <= 2^-25 / S <= 2^-39 bound
 // (fp16 subnormal spacing), far under the fp32 rounding of the products they feed.
+// GELU keeps the argument: |gelu(z)| = |z| Phi(z) <= |z| <= ||a|| M1 + Mb (0 <= Phi <= 1), so
+// the same S holds. Its hidden values are signed (gelu(z) in [-0.17, 0) for z < 0): split8_f16
+// splits signed values as it does linear1's signed A operand (hi = RNE fp16 of the scaled value,
+// lo = fp16 of value - hi by one fma, both sign-symmetric).
 //
 // Weight images: W1 (F, d) is the plain fgr_split_weights_h3 image ([panel][kstep][term][g][16]
 // x 16 B, then the F per-row inverse scales); W2 (d, F) the chunk-major image of
@@ -441,6 +448,11 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
 // Per step and wave: 64 x 16-B weight loads per lane (its 32 KB of W1 and 32 KB of W2), 96 LDS
 // fragment reads, 384 MFMAs; 8 barriers per launch at F = 1024. The weight loads run 3 groups
 // (12 loads) ahead of their MFMAs through a 4-group register ring.
+//
+// ACT = FGR_ACT_GELU: the hidden epilogue forms h S = (S z) Phi(z) instead of max(S z, 0), with
+// z = (S z) / S by a multiplication with 2^-e (exact: S = 2^e, taken from S's exponent) and
+// Phi(z) = 0.5 (1 + erf(z / sqrt 2)) by gelu_scaled below, 8 RT values per lane and step;
+// everything else is the ReLU kernel's code. Built for RT = 3 only (see the dispatcher).
 constexpr int kV2Groups = 16;          // load groups per step: 8 linear1 k32 steps, 8 linear2 halves
 constexpr int kCusFfn = 256;           // MI355X compute units (one block per CU)
 #ifndef FGR_FFN_RING
@@ -462,11 +474,42 @@ __device__ __forceinline__ void wait_vm_only(int n) {
 #undef FGR_VMW
 }
 
+// (S z) Phi(z) for sz = S z and isq = 1 / (S sqrt 2): the scaled GELU of a hidden value
+//
+// Phi(z) = 0.5 (1 + erf(a)), a = z / sqrt 2, is evaluated in straight-line code, not by the
+// device library's erff: that one branches per element (85 branches in the RT = 3 kernel), and
+// around them the register allocator put acc1 and part of accy into scratch (208 / 272 B per
+// lane at RT = 3 / 4). Both ranges are computed and one is selected: |a| <= 0.927734375:
+// erf(a) = a + a p(a^2); above: erfc(|a|) = exp(r(|a|)) (the two minimax polynomials of
+// N. Juffa's erff, <= 1 ulp of erf each), and then Phi = 0.5 exp(r) for a < 0, 1 - 0.5 exp(r)
+// for a > 0 -- the negative tail without the 1 + erf cancellation. |Phi error| <= 6e-8.
+__device__ __forceinline__ float gelu_scaled(float sz, float isq) {
+    const float a = sz * isq, t = fabsf(a), s = a * a;
+    float r = fmaf(-1.72853470e-5f, t, 3.83197126e-4f);
+    const float u = fmaf(-3.88396438e-3f, t, 2.42546219e-2f);
+    r = fmaf(r, s, u);
+    r = fmaf(r, t, -1.06777877e-1f);
+    r = fmaf(r, t, -6.34846687e-1f);
+    r = fmaf(r, t, -1.28717512e-1f);
+    r = fmaf(r, t, -t);
+    const float e = 0.5f * __expf(r);
+    const float tail = a < 0.f ? e : 1.f - e;
+    float q = -5.96761703e-4f;
+    q = fmaf(q, s, 4.99119423e-3f);
+    q = fmaf(q, s, -2.67681349e-2f);
+    q = fmaf(q, s, 1.12819925e-1f);
+    q = fmaf(q, s, -3.76125336e-1f);
+    q = fmaf(q, s, 1.28379166e-1f);
+    const float mid = fmaf(0.5f, fmaf(q, a, a), 0.5f);
+    return sz * (t > 0.927734375f ? tail : mid);
+}
+
 // RT row tiles per block (16 RT rows): 4, or 3 where 48-row blocks still fit the CUs in one
 // round (ModelNet's 9544 rows: 199 blocks instead of 150 -- every block 25 % shorter)
-template <int RT>
+template <int RT, int ACT = FGR_ACT_RELU>
 __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
     static_assert(RT >= 1 && RT <= 4, "row tiles");
+    static_assert(ACT == FGR_ACT_RELU || ACT == FGR_ACT_GELU, "activation");
     __shared__ u32x4 act[RT * kFfnKS * 2 * 64];           // [row tile][k32 step][term][lane]
     __shared__ u32x4 hbuf[2][4][RT][2][64];               // [step & 1][src wave][row tile][term][lane]
     __shared__ float4 cw1[kFfnMaxF / 4], cb1[kFfnMaxF / 4];
@@ -659,7 +702,7 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 6 * RT, 0);
                 __builtin_amdgcn_sched_barrier(0);                      // nothing crosses groups
                 if (j == 7) {
-                    // bias + ReLU + S, split: the chunk's linear2 B fragments -> the hand-off buffer
+                    // bias + activation + S, split: the chunk's linear2 B fragments -> the hand-off buffer
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
                         const float2 rp = rowpar[16 * rt + c];
@@ -668,10 +711,22 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
                         for (int pp = 0; pp < 2; ++pp) {
                             const int n = 32 * ch + 16 * pp + 4 * g;
                             const float4 w4 = cw1[n / 4], b4 = cb1[n / 4];
-                            hv[4 * pp + 0] = fmaxf(fmaf(acc1[rt][pp][0], rp.x * w4.x, rp.y * b4.x), 0.f);
-                            hv[4 * pp + 1] = fmaxf(fmaf(acc1[rt][pp][1], rp.x * w4.y, rp.y * b4.y), 0.f);
-                            hv[4 * pp + 2] = fmaxf(fmaf(acc1[rt][pp][2], rp.x * w4.z, rp.y * b4.z), 0.f);
-                            hv[4 * pp + 3] = fmaxf(fmaf(acc1[rt][pp][3], rp.x * w4.w, rp.y * b4.w), 0.f);
+                            if constexpr (ACT == FGR_ACT_RELU) {
+                                hv[4 * pp + 0] = fmaxf(fmaf(acc1[rt][pp][0], rp.x * w4.x, rp.y * b4.x), 0.f);
+                                hv[4 * pp + 1] = fmaxf(fmaf(acc1[rt][pp][1], rp.x * w4.y, rp.y * b4.y), 0.f);
+                                hv[4 * pp + 2] = fmaxf(fmaf(acc1[rt][pp][2], rp.x * w4.z, rp.y * b4.z), 0.f);
+                                hv[4 * pp + 3] = fmaxf(fmaf(acc1[rt][pp][3], rp.x * w4.w, rp.y * b4.w), 0.f);
+                            } else {
+                                // 1 / S from S's exponent (frexp exponent of 2^e is e + 1); in
+                                // units of 1 / sqrt 2: erf's argument is (S z) * isq
+                                const float isq =
+                                    __builtin_ldexpf(0.70710678118654752440f,
+                                                     1 - __builtin_amdgcn_frexp_expf(rp.y));
+                                hv[4 * pp + 0] = gelu_scaled(fmaf(acc1[rt][pp][0], rp.x * w4.x, rp.y * b4.x), isq);
+                                hv[4 * pp + 1] = gelu_scaled(fmaf(acc1[rt][pp][1], rp.x * w4.y, rp.y * b4.y), isq);
+                                hv[4 * pp + 2] = gelu_scaled(fmaf(acc1[rt][pp][2], rp.x * w4.z, rp.y * b4.z), isq);
+                                hv[4 * pp + 3] = gelu_scaled(fmaf(acc1[rt][pp][3], rp.x * w4.w, rp.y * b4.w), isq);
+                            }
                         }
                         u32x4 h, l;
                         split8_f16(hv, 1.f, h, l);
@@ -810,15 +865,34 @@ extern "C" int fgr_ffn_f16x3_supported(int32_t m, int32_t d, int32_t f) {
     return (m > 0 && d == kFfnD && f >= 64 && f % 64 == 0 && f <= kFfnMaxF) ? 1 : 0;
 }
 
+extern "C" int fgr_ffn_f16x3_act_supported(int32_t m, int32_t d, int32_t f, int32_t act) {
+    if (act == FGR_ACT_RELU) return fgr_ffn_f16x3_supported(m, d, f);
+    // GELU lives in the weight-split kernel only (steps of 128 hidden units)
+    if (act == FGR_ACT_GELU) return (fgr_ffn_f16x3_supported(m, d, f) && f % 128 == 0) ? 1 : 0;
+    return 0;
+}
+
 extern "C" int fgr_ffn_f16x3(const float* x, int64_t ldx, const float* gamma, const float* beta,
                              float eps, const void* w1_img, const float* b1, const void* w2_img,
                              const float* b2, const float* bound, float* out, int64_t ldo,
                              int32_t m, int32_t d, int32_t f, void* stream) {
+    return fgr_ffn_f16x3_act(x, ldx, gamma, beta, eps, w1_img, b1, w2_img, b2, bound, out, ldo, m,
+                             d, f, FGR_ACT_RELU, stream);
+}
+
+extern "C" int fgr_ffn_f16x3_act(const float* x, int64_t ldx, const float* gamma,
+                                 const float* beta, float eps, const void* w1_img, const float* b1,
+                                 const void* w2_img, const float* b2, const float* bound,
+                                 float* out, int64_t ldo, int32_t m, int32_t d, int32_t f,
+                                 int32_t act, void* stream) {
+    FGR_REQUIRE(act == FGR_ACT_RELU || act == FGR_ACT_GELU,
+                "fgr_ffn_f16x3_act: act %d (FGR_ACT_RELU or FGR_ACT_GELU)", act);
     FGR_REQUIRE(x && gamma && beta && w1_img && b1 && w2_img && b2 && bound && out && m >= 0 &&
                     ldx >= d && ldo >= d && eps >= 0.f,
                 "fgr_ffn_f16x3: bad arguments");
-    FGR_REQUIRE(m == 0 || fgr_ffn_f16x3_supported(m, d, f),
-                "fgr_ffn_f16x3: d %d, hidden %d not supported (fgr_ffn_f16x3_supported)", d, f);
+    FGR_REQUIRE(m == 0 || fgr_ffn_f16x3_act_supported(m, d, f, act),
+                "fgr_ffn_f16x3: d %d, hidden %d, act %d not supported (fgr_ffn_f16x3_act_supported)",
+                d, f, act);
     const uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) |
                          reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(w1_img) |
                          reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(w2_img) |
@@ -844,7 +918,14 @@ extern "C" int fgr_ffn_f16x3(const float* x, int64_t ldx, const float* gamma, co
     static const int rt_env = [] { const char* e = getenv("FGR_FFN_RT"); return e ? atoi(e) : 0; }();
     const int rt = (rt_env >= 1 && rt_env <= 4) ? rt_env
                    : ((m + 47) / 48 <= kCusFfn && (m + 63) / 64 < kCusFfn) ? 3 : 4;
-    if (ver == 2 && f % 128 == 0) {
+    if (act == FGR_ACT_GELU) {
+        // the weight-split kernel whatever FGR_FFN_V / FGR_FFN_RT say (f % 128 == 0:
+        // _act_supported), always with 48-row blocks: the RT = 4 GELU instantiation does not
+        // fit the registers (272 B of scratch per lane; RT = 3: 216 VGPRs, none), so it is not
+        // built, and row counts past 48 x 256 take more than one round of the CUs
+        const unsigned nb = (unsigned)((m + 47) / 48);
+        hipLaunchKernelGGL((ffn_nsplit_kernel<3, FGR_ACT_GELU>), dim3(nb), dim3(256), 0, st, a);
+    } else if (ver == 2 && f % 128 == 0) {
         const unsigned nb = (unsigned)((m + 16 * rt - 1) / (16 * rt));
         switch (rt) {
             case 1: hipLaunchKernelGGL(ffn_nsplit_kernel<1>, dim3(nb), dim3(256), 0, st, a); break;

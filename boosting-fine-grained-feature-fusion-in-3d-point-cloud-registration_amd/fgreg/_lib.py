@@ -72,6 +72,11 @@ SIGNATURES = {
     'fgr_ffn_f16x3_supported': [_i32, _i32, _i32],
     'fgr_ffn_f16x3': [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32,
                       _i32, _vp],
+    'fgr_ffn_f16x3_act_supported': [_i32, _i32, _i32, _i32],
+    'fgr_ffn_f16x3_act': [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
+                          _i32, _i32, _i32, _vp],
+    'fgr_gelu_fwd': [_vp, _vp, _i64, _vp],
+    'fgr_gelu_bwd': [_vp, _vp, _vp, _i64, _vp],
     'fgr_pos_mlp_f16x3_supported': [_i64, _i32],
     'fgr_pos_mlp_f16x3': [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                           _i64, _vp],
@@ -166,6 +171,7 @@ SIGNATURES = {
 
 NB_INDEX, NB_DIST = 0, 1
 ACT_NONE, ACT_LEAKY, ACT_RELU, ACT_RELU_RES_LEAKY = 0, 1, 2, 3
+ACT_GELU = 4        # ops.ffn / autograd.linear_t only: no GEMM entry point takes it
 
 _lib = None
 

@@ -37,7 +37,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from . import linear as lin
 from .linear import linear
-from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU, _c, _dev, _ptr, _stream
+from .ops import ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, _c, _dev, _ptr, _stream
 
 
 def colsum(x: torch.Tensor) -> torch.Tensor:
@@ -108,10 +108,14 @@ def _relu_mask(dy, y):
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, residual, act, cache=True):
-        assert act in (ACT_NONE, ACT_RELU)
-        y = linear(x, w, b, act=act, residual=residual, cache=cache)
+        assert act in (ACT_NONE, ACT_RELU, ACT_GELU)
         ctx.mode = lin.MODE          # the backward's products run in the forward's mode
         ctx.act, ctx.has_b, ctx.has_r, ctx.cache = act, b is not None, residual is not None, cache
+        if act == ACT_GELU:          # no GEMM epilogue has it: y = gelu(z), z saved
+            z = linear(x, w, b, residual=residual, cache=cache)
+            ctx.save_for_backward(x, w, z)
+            return ops.gelu(z)
+        y = linear(x, w, b, act=act, residual=residual, cache=cache)
         ctx.save_for_backward(x, w, y if act == ACT_RELU else None)
         return y
 
@@ -121,6 +125,8 @@ class _LinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         if ctx.act == ACT_RELU:
             dy = _relu_mask(dy, y)
+        elif ctx.act == ACT_GELU:    # y holds z, the GELU's input
+            dy = ops.gelu_backward(y, dy)
         dx = dw = db = None
         want_db = ctx.has_b and ctx.needs_input_grad[2]
         with lin.mode_scope(ctx.mode):

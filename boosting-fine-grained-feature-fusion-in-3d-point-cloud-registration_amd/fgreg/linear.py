@@ -145,13 +145,23 @@ def weight_image(w: torch.Tensor, transpose=False, tag=None, mode=None, cache=Tr
     return ent
 
 
+def _no_gelu(act):
+    """The GEMM entry points take ACT_NONE .. ACT_RELU_RES_LEAKY; at least one of their
+    dispatchers runs an unknown code as "no activation", so ACT_GELU must not reach them."""
+    if act == ops.ACT_GELU:
+        raise _lib.FgrError('ACT_GELU is not a GEMM epilogue: use act=ACT_NONE, then ops.gelu_ '
+                            '(or ops.ffn / autograd.linear_t, which take it)')
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias=None, act=ACT_NONE, residual=None,
            transpose=False, tag=None, out=None, cache=True, rows=None) -> torch.Tensor:
     """act(A @ W^T + bias (+ residual)) with A = x and W = w (n, k), or w[r0:r1] for ``rows``
     = (r0, r1), or W = w.reshape(k, n).t() if transpose (e.g. KPConv weights (K, Cin, Cout)
     used as (K*Cin, Cout)), or W = w.reshape(-1, w.shape[-1]) if transpose == 'flat' (the
     backward's d_wf = dout W2^T). ACT_RELU_RES_LEAKY applies the residual after the ReLU:
-    LeakyReLU_0.1(ReLU(A @ W^T + bias) + residual)."""
+    LeakyReLU_0.1(ReLU(A @ W^T + bias) + residual). ACT_GELU is refused: no GEMM epilogue has
+    it (callers run act=ACT_NONE, then ops.gelu_)."""
+    _no_gelu(act)
     if transpose == 'flat':
         k = w.shape[-1]
         n = w.numel() // k
@@ -211,6 +221,7 @@ def linear_ln(x: torch.Tensor, norm, w: torch.Tensor, bias=None, act=ACT_NONE, a
     else ops.layernorm then linear() -- the same arithmetic in two launches. ``side`` =
     (norm2, out2): also out2 = norm2(x) (the encoder's output norm of the previous layer; the
     fused launch writes it from the same statistics, fgr_gemm_f16x3_ln_out2; needs ``add``)."""
+    _no_gelu(act)
     m, k = x.shape
     n = w.shape[0]
     assert w.shape[1] == k and norm.weight.numel() == k

@@ -14,7 +14,8 @@ from typing import Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_RELU_RES_LEAKY, NB_DIST, NB_INDEX  # noqa: F401
+from ._lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_RELU_RES_LEAKY,  # noqa: F401
+                   NB_DIST, NB_INDEX)
 
 
 def _ptr(t):
@@ -871,17 +872,18 @@ def qkv_attention(h, w_img, bias, q_off, kv_seg, max_len, n_head, mode='f16x3'):
 FFN_FUSE = os.environ.get('FGREG_FFN_FUSE', '1') != '0'
 
 
-def ffn_supported(m, d, f) -> bool:
-    """True if the pre-norm feed-forward sub-layer of an (m, d) input with hidden width f runs
-    as one launch (fgr_ffn_f16x3: d = 256, the ModelNet transformer; FGREG_FFN_FUSE=0 off)."""
-    return FFN_FUSE and bool(_lib.load().fgr_ffn_f16x3_supported(m, d, f))
+def ffn_supported(m, d, f, act=ACT_RELU) -> bool:
+    """True if the pre-norm feed-forward sub-layer of an (m, d) input with hidden width f and
+    activation act (ACT_RELU or ACT_GELU) runs as one launch (fgr_ffn_f16x3_act: d = 256, the
+    ModelNet transformer; GELU: f % 128 == 0 as well; FGREG_FFN_FUSE=0 off)."""
+    return FFN_FUSE and bool(_lib.load().fgr_ffn_f16x3_act_supported(m, d, f, act))
 
 
-def ffn(x, norm, w1_img, b1, w2_img, b2, bound, out=None) -> torch.Tensor:
-    """x + linear2(ReLU(linear1(norm(x)))) in one launch (transformers.py:231-238):
-    w1_img = linear.weight_image(linear1.weight, mode='f16x3'), w2_img =
-    linear.weight_image(linear2.weight, mode='ffn2'), bound (2,) = {max_j ||W1_j||, max |b1|}
-    on the device."""
+def ffn(x, norm, w1_img, b1, w2_img, b2, bound, out=None, act=ACT_RELU) -> torch.Tensor:
+    """x + linear2(act(linear1(norm(x)))) in one launch (transformers.py:231-238), act =
+    ACT_RELU or ACT_GELU (the exact erf GELU): w1_img = linear.weight_image(linear1.weight,
+    mode='f16x3'), w2_img = linear.weight_image(linear2.weight, mode='ffn2'), bound (2,) =
+    {max_j ||W1_j||, max |b1|} on the device."""
     _dev(x, b1, b2, bound)
     m, d = x.shape
     f = b1.numel()
@@ -892,11 +894,43 @@ def ffn(x, norm, w1_img, b1, w2_img, b2, bound, out=None) -> torch.Tensor:
     if out is None:
         out = torch.empty((m, d), dtype=torch.float32, device=x.device)
     t0 = _begin('gemm', ('ffn', m, d, f))
-    _lib.check(_lib.load().fgr_ffn_f16x3(
+    _lib.check(_lib.load().fgr_ffn_f16x3_act(
         _ptr(x), x.stride(0), _ptr(g), _ptr(b), float(norm.eps), _ptr(w1_img.img), _ptr(b1),
-        _ptr(w2_img.img), _ptr(b2), _ptr(bound), _ptr(out), out.stride(0), m, d, f, _stream()),
-        'fgr_ffn_f16x3')
+        _ptr(w2_img.img), _ptr(b2), _ptr(bound), _ptr(out), out.stride(0), m, d, f, int(act),
+        _stream()), 'fgr_ffn_f16x3_act')
     _end('gemm', t0, 4 * m * d * f)
+    return out
+
+
+def gelu(z, out=None) -> torch.Tensor:
+    """The exact GELU 0.5 z (1 + erf(z / sqrt 2)) of a contiguous fp32 tensor of any shape
+    (fgr_gelu_fwd: F.gelu's fp32 formula); ``out`` may be z itself."""
+    _dev(z, out)
+    assert z.dtype == torch.float32 and z.is_contiguous()
+    if out is None:
+        out = torch.empty_like(z)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == z.shape
+    _lib.check(_lib.load().fgr_gelu_fwd(_ptr(z), _ptr(out), z.numel(), _stream()), 'fgr_gelu_fwd')
+    return out
+
+
+def gelu_(z) -> torch.Tensor:
+    """gelu in place."""
+    return gelu(z, out=z)
+
+
+def gelu_backward(z, dy, out=None) -> torch.Tensor:
+    """dy * d gelu(z) / dz = dy (Phi(z) + z phi(z)) (fgr_gelu_bwd); z = the GELU's input,
+    ``out`` may be dy itself."""
+    _dev(z, dy, out)
+    assert z.dtype == torch.float32 and z.is_contiguous()
+    dy = _c(dy, torch.float32)
+    assert dy.shape == z.shape
+    if out is None:
+        out = torch.empty_like(z)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == z.shape
+    _lib.check(_lib.load().fgr_gelu_bwd(_ptr(z), _ptr(dy), _ptr(out), z.numel(), _stream()),
+               'fgr_gelu_bwd')
     return out
 
 

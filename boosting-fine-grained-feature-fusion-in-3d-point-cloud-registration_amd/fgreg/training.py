@@ -100,7 +100,7 @@ def _residual(x, y_fn, lin, p):
 
 def _ffn_hidden(layer, h, p):
     """activation(linear1(h)), then the FFN's own dropout (:102, :233) when p > 0."""
-    h = linear_t(h, layer.linear1.weight, layer.linear1.bias, act=ACT_RELU)
+    h = linear_t(h, layer.linear1.weight, layer.linear1.bias, act=layer.act)
     return F.dropout(h, p, training=True) if p > 0.0 else h
 
 

@@ -90,8 +90,16 @@ class TransformerCrossEncoderLayer(nn.Module):
         super().__init__()
         if attention_type != 'dot_prod':
             raise NotImplementedError(attention_type)
-        if activation != 'relu':
-            raise NotImplementedError('transformer_act other than relu is not in the configs')
+        # _get_activation_fn (transformers.py:265-273): relu | gelu | glu, else RuntimeError
+        if activation == 'glu':
+            raise NotImplementedError(
+                "transformer_act 'glu': the reference's own F.glu halves the hidden width "
+                '(dim_feedforward -> dim_feedforward / 2), so the reference itself fails in '
+                'linear2; there is nothing to reproduce')
+        if activation not in ('relu', 'gelu'):
+            raise RuntimeError(f'transformer_act must be relu or gelu, not {activation!r}')
+        self.activation = activation
+        self.act = ops.ACT_GELU if activation == 'gelu' else ops.ACT_RELU
         self.self_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
         self.multihead_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
@@ -201,11 +209,14 @@ class TransformerCrossEncoderLayer(nn.Module):
                    residual=x)
         # position-wise feed-forward (:231-238): one launch where supported (ops.ffn: the
         # hidden activations stay on chip), else linear_ln (or layernorm + linear) then linear
-        if lin.MODE == 'f16x3' and ops.ffn_supported(n, d, self.linear1.out_features):
+        if lin.MODE == 'f16x3' and ops.ffn_supported(n, d, self.linear1.out_features, self.act):
             return ops.ffn(x, self.norm3, lin.weight_image(self.linear1.weight, mode='f16x3'),
                            self.linear1.bias, lin.weight_image(self.linear2.weight, mode='ffn2'),
-                           self.linear2.bias, self._ffn_bound()), None
-        h = linear_ln(x, self.norm3, self.linear1.weight, self.linear1.bias, act=ops.ACT_RELU)
+                           self.linear2.bias, self._ffn_bound(), act=self.act), None
+        if self.act == ops.ACT_GELU:      # no GEMM epilogue has GELU: fp32, in place, between
+            h = ops.gelu_(linear_ln(x, self.norm3, self.linear1.weight, self.linear1.bias))
+        else:
+            h = linear_ln(x, self.norm3, self.linear1.weight, self.linear1.bias, act=ops.ACT_RELU)
         return linear(h, self.linear2.weight, self.linear2.bias, residual=x), None
 
     def _ffn_bound(self):
@@ -239,7 +250,10 @@ class TransformerCrossEncoderLayer(nn.Module):
         t = linear(o, self.multihead_attn.out_proj.weight, self.multihead_attn.out_proj.bias,
                    residual=x)
         x = ops.layernorm(t, self.norm2.weight, self.norm2.bias, self.norm2.eps)       # :163
-        h = linear(x, self.linear1.weight, self.linear1.bias, act=ops.ACT_RELU)        # :167-169
+        if self.act == ops.ACT_GELU:                                                   # :167-169
+            h = ops.gelu_(linear(x, self.linear1.weight, self.linear1.bias))
+        else:
+            h = linear(x, self.linear1.weight, self.linear1.bias, act=ops.ACT_RELU)
         t = linear(h, self.linear2.weight, self.linear2.bias, residual=x)
         return ops.layernorm(t, self.norm3.weight, self.norm3.bias, self.norm3.eps)
 

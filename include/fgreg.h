@@ -50,7 +50,10 @@ enum {
 /* activation codes; FGR_ACT_RELU_RES_LEAKY (the f16x3 GEMMs only) applies the residual AFTER
  * the ReLU: C = LeakyReLU_0.1(ReLU(A.W + bias) + R) -- a Res2Net block output plus its
  * identity shortcut (finegrained_kpconv_blocks.py:715-725) in one epilogue. */
-enum { FGR_ACT_NONE = 0, FGR_ACT_LEAKY = 1, FGR_ACT_RELU = 2, FGR_ACT_RELU_RES_LEAKY = 3 };
+enum { FGR_ACT_NONE = 0, FGR_ACT_LEAKY = 1, FGR_ACT_RELU = 2, FGR_ACT_RELU_RES_LEAKY = 3,
+       /* the exact (erf) GELU: fgr_ffn_f16x3_act only. NO GEMM entry point takes it (their
+        * epilogues have no GELU; callers run the GEMM with FGR_ACT_NONE, then fgr_gelu_fwd) */
+       FGR_ACT_GELU = 4 };
 
 int fgr_abi_version(void);
 const char* fgr_last_error(void);
@@ -169,6 +172,19 @@ int fgr_layernorm_dual(const float* x, int64_t n, int32_t d, const float* gamma,
 /* out = a + b over n floats: the post-norm layer's with_pos_embed (transformers.py:121-124,
  * pre_norm: False; the pre-norm path fuses this add into fgr_layernorm). */
 int fgr_add(const float* a, const float* b, int64_t n, float* out, void* stream);
+
+/* Elementwise exact GELU over n floats (`transformer_act: gelu`, transformers.py:265-273 =
+ * F.gelu) and its derivative, the formulas torch's fp32 F.gelu and its gradient evaluate:
+ *   fgr_gelu_fwd:  y[i]  = 0.5 z[i] (1 + erf(z[i] / sqrt 2))
+ *   fgr_gelu_bwd:  dz[i] = dy[i] (Phi(z[i]) + z[i] phi(z[i])),  Phi(z) = 0.5 (1 + erf(z / sqrt 2)),
+ *                                                                phi(z) = exp(-z^2 / 2) / sqrt(2 pi)
+ * The tails are exact: z <= -6 gives (-)0, z >= 6 gives z (and dz = dy), no NaN for any finite
+ * z. All pointers 16-B aligned (FGR_E_ARG otherwise; n need not be a multiple of 4). In place
+ * is allowed (y == z; dz == dy or dz == z); an output that overlaps an input partially is
+ * FGR_E_ARG. n = 0 returns FGR_OK and touches nothing (pointers may be NULL); n < 0 or a null
+ * pointer with n > 0 is FGR_E_ARG. Writes exactly n floats. */
+int fgr_gelu_fwd(const float* z, float* y, int64_t n, void* stream);
+int fgr_gelu_bwd(const float* z, const float* dy, float* dz, int64_t n, void* stream);
 
 /* PositionEmbeddingCoordsSine (position_embedding.py:29-49) for 3-D input. */
 int fgr_sine_pos_embed(const float* xyz, int64_t n, int32_t d_model, float temperature,
@@ -291,7 +307,15 @@ int fgr_gemm_f16x3_ln_out2(const float* x, int64_t ldx, const float* gamma, cons
  * ||linear1.weight[j]||_2, max_j |b1[j]|} (sets the hidden values' fp16 scale). All pointers
  * 16-B aligned, row strides multiples of 4. fgr_ffn_f16x3_supported(m, d, f): d = 256,
  * 64 <= f <= 2048, f % 64 == 0 (the ModelNet transformer). Replaces the two-launch
- * linear1 (fgr_gemm_f16x3_ln) -> linear2 (fgr_gemm_f16x3_ws, residual) sequence. */
+ * linear1 (fgr_gemm_f16x3_ln) -> linear2 (fgr_gemm_f16x3_ws, residual) sequence.
+ * fgr_ffn_f16x3_act: the same with the activation as an argument, FGR_ACT_RELU (exactly
+ * fgr_ffn_f16x3, which calls it) or FGR_ACT_GELU (the exact erf GELU, 0.5 z (1 + erf(z / sqrt
+ * 2)), formed on the fp32 hidden value before its fp16 split); any other code is FGR_E_ARG.
+ * fgr_ffn_f16x3_act_supported(m, d, f, act): for FGR_ACT_RELU what fgr_ffn_f16x3_supported
+ * returns; for FGR_ACT_GELU that and f % 128 == 0 (GELU exists in the default, weight-split
+ * kernel only; the FGR_FFN_V environment switch is ignored for it); 0 for any other code.
+ * Unsupported GELU shapes run as fgr_gemm_f16x3_ln (FGR_ACT_NONE), fgr_gelu_fwd in place, then
+ * fgr_gemm_f16x3_ws (residual). */
 int fgr_split_weights_ffn2_bytes(int32_t n, int32_t k, size_t* bytes);
 int fgr_split_weights_ffn2(const float* w, int32_t n, int32_t k, int64_t stride_n,
                            int64_t stride_k, void* img, void* stream);
@@ -300,6 +324,11 @@ int fgr_ffn_f16x3(const float* x, int64_t ldx, const float* gamma, const float* 
                   const void* w1_img, const float* b1, const void* w2_img, const float* b2,
                   const float* bound, float* out, int64_t ldo, int32_t m, int32_t d, int32_t f,
                   void* stream);
+int fgr_ffn_f16x3_act_supported(int32_t m, int32_t d, int32_t f, int32_t act);
+int fgr_ffn_f16x3_act(const float* x, int64_t ldx, const float* gamma, const float* beta,
+                      float eps, const void* w1_img, const float* b1, const void* w2_img,
+                      const float* b2, const float* bound, float* out, int64_t ldo, int32_t m,
+                      int32_t d, int32_t f, int32_t act, void* stream);
 
 /* PositionEmbeddingLearned (position_embedding.py:52-71) in one launch: the per-point MLP
  *   out[r] = L4(ReLU(L3(ReLU(L2(ReLU(L1(ReLU(L0(xyz[r])))))))))

@@ -17,6 +17,7 @@
 // * fgr_attention_bf16: the flash attention of attention16.hip with single-term bf16 K / V
 //   images ([k-step][g 4][key 64] / [key 64][DH] with the ds_read_b64_tr_b16 swizzle), Q and
 //   P rounded to bf16 in registers, head_dim 32 or 64.
+#include <cstring>
 #include <type_traits>
 
 #include "common.h"
@@ -521,7 +522,10 @@ inline bool splitk_shape(int m, int n, int k) {        // as gemm16.hip
 // narrow outputs with long contractions: the 64 x 64 LDS-DMA g5 ('X', gemm5.hip; measured
 // 1.2-1.5x faster there); few tiles (<= 400 of 64 x 64) with K >= 512 and the short-M
 // K >= 2048 layers: the two-k-group g5 ('S', 'T', 'W'); otherwise the register-staged
-// kernel below ('z'; FGR_GEMM_BF16_TILE A..Z forces a g5 variant, anything else it)
+// kernel below ('z'). FGR_GEMM_BF16_TILE forces one letter of kBf16Tiles for tuning (any other
+// letter is returned as it is and refused by the callers); a forced g5 letter with
+// K % 8 != 0 runs the register-staged kernel
+extern const char kBf16Tiles[] = "zABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789";
 char bf16_tile(int m, int n, int k) {
     const char* force = getenv("FGR_GEMM_BF16_TILE");
     if (force && force[0]) return force[0];
@@ -582,7 +586,9 @@ static int gemm_bf16_impl(const float* a, int64_t lda, const void* w_img, float*
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
     const char cfg = bf16_tile(m, n, k);
-    if (((cfg >= 'A' && cfg <= 'Z') || (cfg >= '0' && cfg <= '9')) && k % 8 == 0) {
+    FGR_REQUIRE(strchr(kBf16Tiles, cfg), "fgr_gemm_bf16: no tile variant '%c' (FGR_GEMM_BF16_TILE: one of %s)",
+                cfg, kBf16Tiles);
+    if (cfg != 'z' && k % 8 == 0) {
         int ks = bf16_ksplit(cfg, m, n, k);
         if (ks > 1 && (!ws || ws_bytes < (size_t)ks * m * n * sizeof(float) ||
                        (reinterpret_cast<uintptr_t>(ws) & 15) != 0))

@@ -29,6 +29,8 @@
 // remapped so the blocks sharing an A row panel run on one XCD (its L2 keeps the panel).
 // 16x16x32 f16 lane maps (lane l, g = l >> 4, c = l & 15): A[i = c][k = 8g + e],
 // B[k = 8g + e][j = c], C[i = 4g + r][j = c].
+#include <cstring>
+
 #include "common.h"
 
 namespace fgr {
@@ -42,6 +44,7 @@ bool gemm_g5_f16x3_qkv(const float* A, int64_t lda, const void* W, int ksteps, c
                        char* kv_img, int2* kv_sc, hipStream_t st);
 int g5_ksplit(int M, int N, int K, int BM, int BN);
 char bf16_tile(int m, int n, int k);
+extern const char kBf16Tiles[];
 int bf16_ksplit(char cfg, int m, int n, int k);
 struct RsLn {
     const float* g; const float* b; const float* add; int64_t ld_add; float eps;
@@ -135,12 +138,12 @@ __device__ __forceinline__ void store_out4(const float (&y)[4], const float* bia
 
 // EPI: staged epilogue -- each wave's scaled (BM/2) x (BN/2) tile parked in LDS (sharing the
 // A / W image space) and written row-major, 16 B per lane over whole row slices.
-template <int BM, int BN, bool KVEC, bool EPI = false>
+template <bool KVEC, bool EPI>
 __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
+    constexpr int BM = 64, BN = 128;                    // v1's one tile ('b', 'y')
     constexpr int TM = BM / 32, TN = BN / 32;          // 16x16 subtiles per wave (m, n)
     constexpr int UA = BM * 4 / 256;                    // A units (8 k of one row) per thread
     constexpr int UW = 8 * BN / 256;                    // W image units per thread
-    static_assert(UA >= 1 && UW >= 1, "tile");
     constexpr int ERS = BN / 2 + 4;                     // staged row stride (floats)
     constexpr int IMG_U = 2 * 4 * BM + 8 * BN;          // A + W images (16-B units)
     constexpr int EPI_U = EPI ? (4 * (BM / 2) * ERS * 4 + 15) / 16 : 0;
@@ -539,201 +542,6 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
 }
 
 // ------------------------------------------------------------------------------------
-// v3: the v2 stage layout (KS k32-steps per stage, double-buffered LDS, one barrier per
-// stage) with a two-deep REGISTER ring: while stage s is multiplied, the global loads of
-// stages s+1 and s+2 are in flight (v2 keeps only s+1 in flight, so every stage waits out
-// most of an L2/HBM round trip). Stage s+1 is split and written to the idle LDS buffer after
-// the MFMAs of stage s, then its registers are refilled with stage s+3. The loop is unrolled
-// by two so every ring index is a compile-time constant (no scratch).
-// ------------------------------------------------------------------------------------
-template <int BM, int BN, int KS, bool KVEC>
-__global__ void __launch_bounds__(256) gemm_f16x3_v3(GemmH3Args p) {
-    constexpr int TM = BM / 32, TN = BN / 32;
-    constexpr int RU = 4 * KS;                          // units (8 k) of a row per stage
-    constexpr int UA = BM * RU / 256;                   // A units per thread per stage
-    constexpr int UW = 8 * BN * KS / 256;               // W units per thread per stage
-    constexpr int ASZ = 8 * BM * KS, WSZ = 8 * BN * KS; // 16-B units per stage
-    static_assert(UA >= 1 && UW >= 1 && (RU == 4 || RU == 8), "tile");
-    __shared__ u32x4 lds[2 * (ASZ + WSZ)];
-    __shared__ int sh_lds[2][BM];
-
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    int t = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
-    const int bm = t / nbn, bn = t % nbn;
-    const int m0 = bm * BM, n0 = bn * BN;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int wn = (wv >> 1) * (BN / 2), wm = (wv & 1) * (BM / 2);
-    const int g = lane >> 4, c = lane & 15;
-    const int npanel = (p.N + 15) / 16;
-
-    const float* arow[UA];
-    int akk[UA], sh[UA];
-#pragma unroll
-    for (int j = 0; j < UA; ++j) {
-        const int u = tid + 256 * j;
-        arow[j] = p.A + (int64_t)min(m0 + u / RU, p.M - 1) * p.lda;
-        akk[j] = 8 * (u % RU);
-        sh[j] = SH_UNSET;
-    }
-    const u32x4* wsrc[UW];
-#pragma unroll
-    for (int j = 0; j < UW; ++j) {
-        const int v = tid + 256 * j;
-        const int panel = min(n0 / 16 + v / (128 * KS), npanel - 1);
-        wsrc[j] = p.W + (int64_t)panel * p.ksteps * 128 + v % (128 * KS);
-    }
-    float4 ar0[UA][2], ar1[UA][2];
-    u32x4 wr0[UW], wr1[UW];
-    auto load = [&](int s, float4 (&ar)[UA][2], u32x4 (&wr)[UW]) {
-#pragma unroll
-        for (int j = 0; j < UA; ++j) {
-            const int k = s * 32 * KS + akk[j];
-            if constexpr (KVEC) {
-                const float* src = arow[j] + min(k, p.K - 8);
-                const float4 x0 = *reinterpret_cast<const float4*>(src);
-                const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
-                const bool ok = k < p.K;
-                ar[j][0] = ok ? x0 : make_float4(0.f, 0.f, 0.f, 0.f);
-                ar[j][1] = ok ? x1 : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float tt[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float xv = arow[j][min(k + e, p.K - 1)];
-                    tt[e] = k + e < p.K ? xv : 0.f;
-                }
-                ar[j][0] = make_float4(tt[0], tt[1], tt[2], tt[3]);
-                ar[j][1] = make_float4(tt[4], tt[5], tt[6], tt[7]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < UW; ++j) wr[j] = wsrc[j][(int64_t)s * 128 * KS];
-    };
-    auto store = [&](int b, const float4 (&ar)[UA][2], const u32x4 (&wr)[UW]) {
-        u32x4* a_img = lds + b * (ASZ + WSZ);
-        u32x4* w_img = a_img + ASZ;
-#pragma unroll
-        for (int j = 0; j < UA; ++j) {
-            const int u = tid + 256 * j;
-            const int row = u / RU, q = u % RU, ks = q >> 2, gg = q & 3;
-            const float x[8] = {ar[j][0].x, ar[j][0].y, ar[j][0].z, ar[j][0].w,
-                                ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
-            float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
-            cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dppf<0xB1>(cm));
-            cm = fmaxf(cm, dppf<0x4E>(cm));
-            if constexpr (RU == 8) cm = fmaxf(cm, dppf<0x141>(cm));
-            if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
-            const float sc = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
-            f16x8 th, tm;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xs = x[e] * sc;
-                const _Float16 h = (_Float16)xs;
-                th[e] = h;
-                tm[e] = (_Float16)(xs - (float)h);
-            }
-            const int r = row ^ (2 * gg);
-            a_img[((ks * 2 + 0) * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, th);
-            a_img[((ks * 2 + 1) * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, tm);
-            if (q == 0) sh_lds[b][row] = sh[j];
-        }
-#pragma unroll
-        for (int j = 0; j < UW; ++j) w_img[tid + 256 * j] = wr[j];
-    };
-
-    f32x4 acc[TN][TM];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int shr[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) shr[i] = SH_UNSET;
-
-    auto compute = [&](int b) {
-        const u32x4* a_img = lds + b * (ASZ + WSZ);
-        const u32x4* w_img = a_img + ASZ;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int shv = sh_lds[b][wm + 16 * i + c];
-            if (__builtin_amdgcn_ballot_w64(shv != shr[i])) {
-                const float f = (shr[i] == SH_UNSET || shv == shr[i])
-                                    ? 1.f : __builtin_ldexpf(1.f, shv - shr[i]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[j][i] *= f;
-                shr[i] = shv;
-            }
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            f16x8 af[TM][2];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int r = (wm + 16 * i + c) ^ (2 * g);
-                af[i][0] = __builtin_bit_cast(f16x8, a_img[((ks * 2 + 0) * 4 + g) * BM + r]);
-                af[i][1] = __builtin_bit_cast(f16x8, a_img[((ks * 2 + 1) * 4 + g) * BM + r]);
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int pp = (wn + 16 * j) >> 4;
-                const u32x4* wb = w_img + pp * 128 * KS + ks * 128 + g * 16 + c;
-                const f16x8 wh = __builtin_bit_cast(f16x8, wb[0]);
-                const f16x8 wl = __builtin_bit_cast(f16x8, wb[64]);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, af[i][0], acc[j][i], 0, 0, 0);
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, af[i][1], acc[j][i], 0, 0, 0);
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, af[i][0], acc[j][i], 0, 0, 0);
-                }
-            }
-        }
-    };
-
-    const int nst = (p.K + 32 * KS - 1) / (32 * KS);
-    load(0, ar0, wr0);
-    if (nst > 1) load(1, ar1, wr1);
-    store(0, ar0, wr0);
-    __syncthreads();
-    if (nst > 2) load(2, ar0, wr0);
-    // iteration s: multiply buffer s&1, stage s+1 from ring (s+1)&1, refill it with s+3
-    for (int s = 0; s < nst; s += 2) {
-        compute(0);
-        if (s + 1 < nst) store(1, ar1, wr1);
-        if (s + 3 < nst) load(s + 3, ar1, wr1);
-        __syncthreads();
-        if (s + 1 >= nst) break;
-        compute(1);
-        if (s + 2 < nst) store(0, ar0, wr0);
-        if (s + 4 < nst) load(s + 4, ar0, wr0);
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm + 16 * i + c;
-        if (m >= p.M) continue;
-        const float rs = __builtin_ldexpf(1.f, -shr[i]);
-        float* crow = p.C + (int64_t)m * p.ldc;
-        const float* rrow = p.R ? p.R + (int64_t)m * p.ldr : nullptr;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn + 16 * j + 4 * g;
-            if (n >= p.N) continue;
-            const float4 ws = *reinterpret_cast<const float4*>(p.wsc + n);
-            const float y[4] = {acc[j][i][0] * rs * ws.x, acc[j][i][1] * rs * ws.y,
-                                acc[j][i][2] * rs * ws.z, acc[j][i][3] * rs * ws.w};
-            store_out4(y, p.bias, rrow, crow, n, p.N, p.act, p.vec_out);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
 // v4: W fragments straight from the image into registers. The f16x3 W image is stored in
 // MFMA fragment order ([panel][kstep][term][g][16] x 16 B), so one wave-load of a panel's
 // term is 1 KB contiguous in lane order -- no LDS round trip for W. The waves split the
@@ -741,7 +549,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v3(GemmH3Args p) {
 // BM activation rows, so no W byte is loaded twice per block; only A is staged (split in
 // registers -> double-buffered LDS, one barrier per k32 step). W fragments of step s+1 are
 // loaded while step s multiplies (register double buffer, loop unrolled by two).
-// Motivation (VERDICT r1 / microbench): v1-v3 stage W through LDS with ds_write_b128, whose
+// Motivation (VERDICT r1 / microbench): v1 and v2 stage W through LDS with ds_write_b128, whose
 // transfer cost (~13 cycles per wave-instruction) plus the fragment reads exceeds the
 // MFMA time of a 64 x 128 step -- they are LDS-bound.
 // ------------------------------------------------------------------------------------
@@ -1133,15 +941,13 @@ split_weights_h3_batch_kernel(const fgr_split_desc* __restrict__ d, int count) {
     split_panel_h3(e.w, e.n, e.k, e.stride_n, e.stride_k, ksteps, wsc, img, (int)(b - e.panel0));
 }
 
-template <int BM, int BN, bool EPI = false>
+template <bool EPI>
 void launch_h3(const GemmH3Args& a, hipStream_t st) {
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
+    const int nbm = (a.M + 63) / 64, nbn = (a.N + 127) / 128;
     if (a.K % 8 == 0)
-        hipLaunchKernelGGL((gemm_f16x3_kernel<BM, BN, true, EPI>), dim3((unsigned)(nbm * nbn)),
-                           dim3(256), 0, st, a);
+        hipLaunchKernelGGL((gemm_f16x3_kernel<true, EPI>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((gemm_f16x3_kernel<BM, BN, false, EPI>), dim3((unsigned)(nbm * nbn)),
-                           dim3(256), 0, st, a);
+        hipLaunchKernelGGL((gemm_f16x3_kernel<false, EPI>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, st, a);
 }
 
 // k32-steps of the image, padded to an even count (v2 stages read 2 per stage)
@@ -1160,17 +966,6 @@ void launch_h3v4(const GemmH3Args& a, hipStream_t st) {
     else
         hipLaunchKernelGGL((gemm_f16x3_v4<BM, BN, false>), dim3((unsigned)(nbm * nbn)), dim3(256),
                            0, st, a);
-}
-
-template <int BM, int BN, int KS>
-void launch_h3v3(const GemmH3Args& a, hipStream_t st) {
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
-    if (a.K % 8 == 0)
-        hipLaunchKernelGGL((gemm_f16x3_v3<BM, BN, KS, true>), dim3((unsigned)(nbm * nbn)),
-                           dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((gemm_f16x3_v3<BM, BN, KS, false>), dim3((unsigned)(nbm * nbn)),
-                           dim3(256), 0, st, a);
 }
 
 template <int BM, int BN, int KS, bool DBUF>
@@ -1249,21 +1044,37 @@ extern "C" int fgr_split_weights_h3(const float* w, int32_t n, int32_t k, int64_
 }
 
 namespace fgr {
-// The tile variant the f16x3 dispatcher picks for a shape (FGR_GEMM16_TILE overrides it).
+// The tile variant the f16x3 dispatcher picks for a shape. The letters that exist (BM x BN =
+// activation rows x output channels); the dispatch below returns e f k (v2), t u (v4), y (v1),
+// z and the g5 S T W X Y, the rest are reachable only through FGR_GEMM16_TILE:
+//   b y          v1  64 x 128 (y: staged row-major epilogue)
+//   e f g h i j k l m  v2  (the table in gemm_f16x3_impl)
+//   t u v w x    v4  (W fragments straight to registers)
+//   z            row-stationary (gemm_rs.hip), K <= 256
+//   A..Z, 0..9   g5 (gemm5.hip dispatch_g5_tile), K % 8 == 0 only
+// (v1's 128-row and 64 x 64 tiles a c d and the v3 register-ring kernel n..s, which no shape
+// ever took, are in the history and in profiles/.)
 // Default per shape (measured on the forward's GEMMs with tools/gemm_tiles.py, device
 // time from HIP-graph replays; profiles/r02_gemm_tiles*.txt): wide outputs take 64 x 128
-// tiles (v4 -- W fragments straight to registers -- for K >= 1024, double-buffered v2
-// for K >= 512), very tall ones 64 x 128; narrow outputs (N <= 256) and short row counts
-// (M <= 4096, N <= 512) the 64 x 64 LDS-DMA g5 ('I') when K % 8 == 0, else the 64 x 64 v4.
-// X / Y are I / B and y is b with the row-major staged epilogue (3-8 % faster;
-// profiles/r02_gemm_tiles_epi.txt, r02_gemm_tiles_by.txt).
+// tiles (v4 for K >= 1024, double-buffered v2 for K >= 512 that is no multiple of 8, else
+// v1), very tall ones 64 x 128; narrow outputs (N <= 256) and short row counts (M <= 4096,
+// N <= 512) the 64 x 64 LDS-DMA g5 ('X') when K % 8 == 0, else the 64 x 64 v4 or v2.
+// The staged epilogue of X / Y / y measured 3-8 % faster than the MFMA-layout stores
+// (profiles/r02_gemm_tiles_epi.txt, r02_gemm_tiles_by.txt).
 // Few tiles (<= 400 of 64 x 64, e.g. the 3DMatch transformer's 2 x 1060 tokens) with
-// K >= 512: the two-k-group g5 ('W', 'T'; 8 waves per block) -- 1.1-1.45x there
+// K >= 512: the two-k-group g5 ('S', 'W', 'T'; 8 waves per block) -- 1.1-1.45x there
 // (profiles/r02_gemm_tiles_splitk*.txt).
+// FGR_GEMM16_TILE forces one letter of kH3Tiles for tuning (any other letter is returned as it
+// is and refused by the callers); a forced g5 letter with K % 8 != 0, like a forced 'z' with
+// unaligned operands, runs h3_tile_kloop's own choice.
+constexpr char kH3Tiles[] = "befghijklmtuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789";
 char h3_tile_kloop(int m, int n, int k);
 char h3_tile(int m, int n, int k) {
     const char* force = getenv("FGR_GEMM16_TILE");
-    if (force && force[0]) return force[0];
+    if (force && force[0]) {
+        int bm, bn;
+        return (k % 8 != 0 && g5_tile(force[0], &bm, &bn)) ? h3_tile_kloop(m, n, k) : force[0];
+    }
     // short contractions over many rows: the row-stationary kernel (gemm_rs.hip) where it
     // measured faster than the k-looped choice (profiles/r03_gemm_rs_sweep3.txt: 9544 x 1792 x
     // 256 1.37x, x 1024 x 256 1.17x, x 768 x 256 1.10x, 57264 x 256 x 256 1.46x, K <= 128 with
@@ -1323,6 +1134,9 @@ extern "C" int fgr_gemm_workspace(int32_t m, int32_t n, int32_t k, int32_t mode,
     FGR_REQUIRE(bytes && m >= 0 && n > 0 && k > 0 && (mode == 0 || mode == 1),
                 "fgr_gemm_workspace: bad arguments");
     const char cfg = mode == 0 ? h3_tile(m, n, k) : bf16_tile(m, n, k);
+    const char* valid = mode == 0 ? kH3Tiles : kBf16Tiles;
+    FGR_REQUIRE(strchr(valid, cfg), "fgr_gemm_workspace: no tile variant '%c' (%s: one of %s)", cfg,
+                mode == 0 ? "FGR_GEMM16_TILE" : "FGR_GEMM_BF16_TILE", valid);
     const int ks = mode == 0 ? h3_ksplit(cfg, m, n, k) : bf16_ksplit(cfg, m, n, k);
     *bytes = ks > 1 ? (size_t)ks * m * n * sizeof(float) : 0;
     return FGR_OK;
@@ -1350,10 +1164,10 @@ static int gemm_f16x3_impl(const float* a, int64_t lda, const void* w_img, float
                  m, n, k, act, vo ? 1 : 0};
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
-    // tile BM x BN (activation rows x output channels): h3_tile; FGR_GEMM16_TILE overrides it
-    // for tuning (a = 128x128, b = 64x128, c = 64x64, d = 128x64, e..x: v2-v4 variants, A..Z,
-    // 0..9: g5)
+    // the tile variant (table above h3_tile); FGR_GEMM16_TILE forces a letter for tuning
     char cfg = h3_tile(m, n, k);
+    FGR_REQUIRE(strchr(kH3Tiles, cfg), "fgr_gemm_f16x3: no tile variant '%c' (FGR_GEMM16_TILE: one of %s)",
+                cfg, kH3Tiles);
     // ws (gemm_ws.hip): K = 256, N = 256 / 768 over many rows, 16-B aligned operands
     if (vec && vo && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0) &&
         getenv("FGR_GEMM16_TILE") == nullptr &&
@@ -1370,8 +1184,9 @@ static int gemm_f16x3_impl(const float* a, int64_t lda, const void* w_img, float
         }
         cfg = h3_tile_kloop(m, n, k);                 // unaligned operands
     }
-    // g5 (gemm5.hip: LDS-DMA pipeline, A split after the read): A..W, K % 8 == 0 only
-    if (((cfg >= 'A' && cfg <= 'Z') || (cfg >= '0' && cfg <= '9')) && k % 8 == 0) {
+    // g5 (gemm5.hip: LDS-DMA pipeline, A split after the read): A..Z, 0..9, K % 8 == 0 only
+    int bm, bn;
+    if (g5_tile(cfg, &bm, &bn) && k % 8 == 0) {
         int ks = h3_ksplit(cfg, m, n, k);
         if (ks > 1 && (!ws || ws_bytes < (size_t)ks * m * n * sizeof(float) ||
                        (reinterpret_cast<uintptr_t>(ws) & 15) != 0))
@@ -1382,8 +1197,11 @@ static int gemm_f16x3_impl(const float* a, int64_t lda, const void* w_img, float
         FGR_CHECK_LAUNCH("gemm_g5");
         return FGR_OK;
     }
-    // v2 variants (BM x BN, KS k32-steps per stage, DBUF) for tuning: e..m
     switch (cfg) {
+        // v1 (64 x 128; y: with the staged epilogue)
+        case 'b': launch_h3<false>(g, st); break;
+        case 'y': launch_h3<true>(g, st); break;
+        // v2 (BM x BN, KS k32-steps per stage, DBUF)
         case 'e': launch_h3v2<64, 64, 2, false>(g, st); break;
         case 'f': launch_h3v2<64, 64, 2, true>(g, st); break;
         case 'g': launch_h3v2<64, 128, 2, false>(g, st); break;
@@ -1393,36 +1211,17 @@ static int gemm_f16x3_impl(const float* a, int64_t lda, const void* w_img, float
         case 'k': launch_h3v2<64, 128, 1, true>(g, st); break;
         case 'l': launch_h3v2<64, 64, 1, true>(g, st); break;
         case 'm': launch_h3v2<128, 64, 2, false>(g, st); break;
-        // v3 (two-deep register ring): n..s
-        case 'n': launch_h3v3<64, 64, 2>(g, st); break;
-        case 'o': launch_h3v3<64, 128, 1>(g, st); break;
-        case 'p': launch_h3v3<64, 128, 2>(g, st); break;
-        case 'q': launch_h3v3<128, 64, 1>(g, st); break;
-        case 'r': launch_h3v3<128, 128, 1>(g, st); break;
-        case 's': launch_h3v3<128, 64, 2>(g, st); break;
-        // v4 (W fragments straight to registers): t..x
+        // v4 (W fragments straight to registers)
         case 't': launch_h3v4<64, 64>(g, st); break;
         case 'u': launch_h3v4<64, 128>(g, st); break;
         case 'v': launch_h3v4<128, 64>(g, st); break;
         case 'w': launch_h3v4<128, 128>(g, st); break;
         case 'x': launch_h3v4<64, 256>(g, st); break;
-        default: break;
+        default:      // a guard: every letter of kH3Tiles is handled above
+            set_error("fgr_gemm_f16x3: tile variant '%c' cannot run %d x %d x %d", cfg, m, n, k);
+            return FGR_E_ARG;
     }
-    if (cfg >= 'e' && cfg <= 'x') {
-        FGR_CHECK_LAUNCH("gemm_f16x3_v2");
-        return FGR_OK;
-    }
-    if (cfg == 'a')
-        launch_h3<128, 128>(g, st);
-    else if (cfg == 'b')
-        launch_h3<64, 128>(g, st);
-    else if (cfg == 'y')                                   // 'b' with the staged epilogue
-        launch_h3<64, 128, true>(g, st);
-    else if (cfg == 'd')
-        launch_h3<128, 64>(g, st);
-    else
-        launch_h3<64, 64>(g, st);
-    FGR_CHECK_LAUNCH("gemm_f16x3_kernel");
+    FGR_CHECK_LAUNCH("gemm_f16x3 (k-looped)");
     return FGR_OK;
 }
 

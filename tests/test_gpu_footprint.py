@@ -107,7 +107,7 @@ def _image(arena, w, split='fgr_split_weights_h3', colmajor=False):
 def _gemm(arena, m, n, k, act, res, mode='f16x3', unaligned=False, ws=None, colmajor=False):
     """One fgr_gemm_<mode>[_ws] call. unaligned: the output starts 4 bytes past a 16-B boundary
     with a row stride that is no multiple of 4 (the scalar-store epilogue, vo == 0,
-    gemm16.hip:1344). ws: None (no-workspace entry point) or a byte count relative to
+    gemm16.hip:1158). ws: None (no-workspace entry point) or a byte count relative to
     fgr_gemm_workspace's answer (0 = exactly that, -16 = 16 fewer over the same buffer)."""
     x, w, b, r = _gemm_data(m, n, k)
     a = arena.put(x, ld=k + 4, name='a')
@@ -135,15 +135,15 @@ def _gemm(arena, m, n, k, act, res, mode='f16x3', unaligned=False, ws=None, colm
 
 RAGGED = [(65, 20, 40), (77, 50, 36), (130, 33, 72)]
 EPILOGUES = [(ACT_NONE, True), (ACT_RELU_RES_LEAKY, True)]
-TILES = list('abcdefghijklmnopqrstuvwxyz') + list('ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789')
+TILES = list('befghijklmtuvwxyz') + list('ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789')
 
 
 @pytest.mark.parametrize('tile', TILES)
 def test_gemm_f16x3_tiles_footprint(gpu, tile, monkeypatch):
     """Every f16x3 tile / pipeline variant (FGR_GEMM16_TILE, read per call by h3_tile,
-    gemm16.hip:1265) on ragged shapes: (65, 20, 40) two row tiles and a partial column tile,
-    (77, 50, 36) K % 8 != 0 -- the register-staged fallback for every g5 letter
-    (gemm16.hip:1374) -- and (130, 33, 72) odd N; bias, residual with ldr = n + 8, plain and
+    gemm16.hip:1073) on ragged shapes: (65, 20, 40) two row tiles and a partial column tile,
+    (77, 50, 36) K % 8 != 0 -- where every g5 letter runs the k-looped dispatcher's own choice
+    (gemm16.hip:1076) -- and (130, 33, 72) odd N; bias, residual with ldr = n + 8, plain and
     ReLU-residual-LeakyReLU epilogues; once with 16-B aligned float4 stores and once through
     the scalar-store epilogue."""
     monkeypatch.setenv('FGR_GEMM16_TILE', tile)
@@ -160,9 +160,9 @@ def test_gemm_f16x3_tiles_footprint(gpu, tile, monkeypatch):
 def test_gemm_f16x3_default_dispatch_footprint(gpu, m, n, k, monkeypatch):
     """The default dispatch one ragged row past its thresholds: K = 256 with >= 4096 rows and
     N in {256, 512, 768, 1024} is the weight-split kernel (gemm_ws_supported, gemm_ws.hip:557,
-    taken only with FGR_GEMM16_TILE unset, gemm16.hip:1359; it has the plain / ReLU epilogues
+    taken only with FGR_GEMM16_TILE unset, gemm16.hip:1173; it has the plain / ReLU epilogues
     and the residual add, gemm_ws.hip:576); >= 8000 rows with K <= 128 and N >= 224, or
-    N >= 640, is the row-stationary 'z' (h3_tile, gemm16.hip:1273)."""
+    N >= 640, is the row-stationary 'z' (h3_tile, gemm16.hip:1084)."""
     monkeypatch.delenv('FGR_GEMM16_TILE', raising=False)
     for act, res in [(ACT_NONE, True), (ACT_RELU, False)] + ([(ACT_RELU_RES_LEAKY, True)] if m == 8001 else []):
         out = _both(lambda ar: _gemm(ar, m, n, k, act, res), gpu)
@@ -172,9 +172,9 @@ def test_gemm_f16x3_default_dispatch_footprint(gpu, m, n, k, monkeypatch):
 
 @pytest.mark.parametrize('mode', ['f16x3', 'bf16'])
 def test_gemm_splitk_exact_workspace(gpu, mode, monkeypatch):
-    """Split-K (2120 x 128 x 1920, splitk_shape via h3_tile_kloop, gemm16.hip:1285) with exactly
+    """Split-K (2120 x 128 x 1920, splitk_shape via h3_tile_kloop, gemm16.hip:1096) with exactly
     fgr_gemm_workspace's bytes, 0xFF-prefilled in the poisoned run; and with ws_bytes 16
-    smaller, which the header says runs unsplit (gemm16.hip:1376) -- same contract, so the same
+    smaller, which the header says runs unsplit (gemm16.hip:1191) -- same contract, so the same
     bound, and the workspace then stays untouched."""
     monkeypatch.delenv('FGR_GEMM16_TILE', raising=False)
     monkeypatch.delenv('FGR_GEMM_BF16_TILE', raising=False)
@@ -219,8 +219,8 @@ def test_gemm_bf16_tiles_footprint(gpu, tile, monkeypatch):
 def test_weight_image_exact_bytes(gpu, split, n, k, colmajor, monkeypatch):
     """Weight images in exact-*_bytes scratch views: (3, 36) and (17, 8) partial 16-row panels and
     K-padding, (200, 1000) the largest of the fused split's range (k <= kSplitFusedK = 1024,
-    gemm16.hip:1219), (33, 1032) past it the scale pass + split pass, and with stride_n == 1 the
-    column-major scale pass (gemm16.hip:1225). The GEMM
+    gemm16.hip:1014), (33, 1032) past it the scale pass + split pass, and with stride_n == 1 the
+    column-major scale pass (gemm16.hip:1020). The GEMM
     consuming the image built over 0x00 and over 0xFF bytes must give bit-identical output
     (the arena checks nothing was written past the reported bytes); the image bytes themselves
     are compared too and a difference is reported as don't-care bytes."""
@@ -320,7 +320,7 @@ def test_ffn_footprint(gpu, m, f, in_place):
 
 @pytest.mark.parametrize('m,d', [(97, 64), (333, 128)])
 def test_corr_head_footprint(gpu, m, d):
-    """fgr_corr_head_f16x3 (two row-stationary launches, gemm16.hip:1516): hidden (m, d) is
+    """fgr_corr_head_f16x3 (two row-stationary launches, gemm16.hip:1314): hidden (m, d) is
     caller scratch of exactly 4 m d bytes, corr (m, 3) and logits (m) contiguous guarded
     outputs, f strided. Bound of test_corr_head_fused_vs_fp64: 1e-5 of each row's
     |.|-weighted magnitude."""
@@ -420,7 +420,7 @@ def test_attention_f16x3_footprint(gpu, d):
 
 @pytest.mark.parametrize('d', [256, 512])
 def test_attention_bf16_footprint(gpu, d):
-    """fgr_attention_bf16 (bf16.hip:630), same cases; test_attention_bf16's bound vs exact fp64
+    """fgr_attention_bf16 (bf16.hip:636), same cases; test_attention_bf16's bound vs exact fp64
     at O(1) scores: 1e-2."""
     def run(ar):
         rc, o, _ = _attn_split(ar, 'fgr_attention_bf16', 8, d)
@@ -433,7 +433,7 @@ def test_attention_bf16_footprint(gpu, d):
 @pytest.mark.parametrize('name', ['fgr_attention_f16x3', 'fgr_attention_bf16'])
 def test_attention_refuses_short_workspace(gpu, name):
     """ws_bytes 16 below the kernel's own need (head dim 64, where fgr_*_workspace reports
-    exactly that) is refused before the first launch (attention16.hip:1090, bf16.hip:653):
+    exactly that) is refused before the first launch (attention16.hip:1090, bf16.hip:659):
     non-zero status, a message, output and workspace untouched."""
     ar = Arena(gpu, poison=True)
     rc, o, ws = _attn_split(ar, name, 8, 512, short=16)
@@ -688,7 +688,7 @@ def _ln_data(m, n, k):
 def test_gemm_ln_footprint(gpu, m, n, k, side, monkeypatch):
     """fgr_gemm_f16x3_ln / _ln_out2 one ragged row past the smallest supported row counts:
     4097 x 768 x 256 the weight-split kernel with the LN prologue (gemm_ws_ln_supported,
-    gemm_ws.hip:567), 8001 x 640 x 256 the row-stationary one (h3_tile 'z', gemm16.hip:1273);
+    gemm_ws.hip:567), 8001 x 640 x 256 the row-stationary one (h3_tile 'z', gemm16.hip:1084);
     x, add, c and out2 strided by + 4. 1e-5 vs fp64 (test_gemm_ln_vs_fp64), the side output
     1e-6 (test_ln_qkv_images_vs_two_launch_path)."""
     monkeypatch.delenv('FGR_GEMM16_TILE', raising=False)
@@ -768,7 +768,7 @@ def test_gemm_ln_qkv_footprint(gpu, monkeypatch):
 @pytest.mark.parametrize('mode', ['f16x3', 'bf16'])
 def test_gemm_qkv_dh64_footprint(gpu, mode, monkeypatch):
     """fgr_gemm_f16x3_qkv / fgr_gemm_bf16_qkv (head dim 64: the staged 64 x 128 g5 epilogue,
-    gemm16.hip:1568 / bf16.hip:694) at m = 130, d = 128, 2 heads: three row tiles, the last with
+    gemm16.hip:1366 / bf16.hip:700) at m = 130, d = 128, 2 heads: three row tiles, the last with
     2 rows, segments [65, 1, 64] crossing tiles; K / V images in exact fgr_kv_image[_bf16]_bytes
     views, consumed by fgr_attention_f16x3_img / _bf16_img. 1e-5 vs fp64 (f16x3,
     test_qkv_images_dh64_vs_two_launch_path), 1e-2 (bf16, test_bf16_qkv_images_vs_two_launch_path)."""

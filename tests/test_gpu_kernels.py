@@ -459,11 +459,52 @@ def test_gemm_ws_dynamic_range(gpu, n):
     assert float(((out - ref32).abs() / den).max()) < 2e-6
 
 
-@pytest.mark.parametrize('tile', list('abcdefghijklmnopqrstuvwxyz') + list('ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'))
+@pytest.mark.parametrize('mode,var,tile', [('f16x3', 'FGR_GEMM16_TILE', 'c'),
+                                           ('f16x3', 'FGR_GEMM16_TILE', 'q'),
+                                           ('bf16', 'FGR_GEMM_BF16_TILE', 'q')])
+def test_gemm_forced_tile_unknown_letter(gpu, mode, var, tile, monkeypatch):
+    """A forced letter outside the dispatcher's list (kH3Tiles, gemm16.hip; kBf16Tiles,
+    bf16.hip) is an FgrError that names the letter, never a kernel; with the variable unset the
+    next call of the same shape gives the right product."""
+    from fgreg import _lib
+    from fgreg import linear as fl
+    monkeypatch.setattr(fl, 'MODE', mode)
+    g = torch.Generator().manual_seed(5)
+    x, w = torch.randn(64, 8, generator=g), torch.randn(16, 8, generator=g)
+    X, W = x.to(gpu), w.to(gpu)
+    monkeypatch.setenv(var, tile)
+    with pytest.raises(_lib.FgrError, match=f"'{tile}'"):
+        fl.linear(X, W)
+    monkeypatch.delenv(var)
+    if mode == 'bf16':
+        ref, tol = x.bfloat16().double() @ w.bfloat16().double().t(), 1e-5
+    else:
+        ref, tol = x.double() @ w.double().t(), 2e-6
+    assert rel_err(fl.linear(X, W), ref) < tol
+
+
+def test_gemm_f16x3_forced_g5_unaligned_k(gpu, monkeypatch):
+    """A forced g5 letter whose contraction the g5 kernels cannot take (K % 8 != 0) runs the
+    k-looped dispatcher's own choice for the shape: bit for bit the unforced result."""
+    from fgreg import linear as fl
+    monkeypatch.setattr(fl, 'MODE', 'f16x3')
+    g = torch.Generator().manual_seed(13)
+    X = torch.randn(77, 36, generator=g).to(gpu)
+    W = torch.randn(50, 36, generator=g).to(gpu)
+    b = torch.randn(50, generator=g).to(gpu)
+    monkeypatch.setenv('FGR_GEMM16_TILE', 'X')
+    forced = fl.linear(X, W, b)
+    monkeypatch.delenv('FGR_GEMM16_TILE')
+    assert torch.equal(forced, fl.linear(X, W, b))
+
+
+@pytest.mark.parametrize('tile', list('befghijklmtuvwxyz') + list('ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'))
 def test_gemm_f16x3_tiles(gpu, tile, monkeypatch):
-    """Every f16x3 tile / pipeline variant (FGR_GEMM16_TILE; A..R: the LDS-DMA g5 kernels of
+    """Every f16x3 tile / pipeline variant (FGR_GEMM16_TILE; lower case: the register-staged
+    v1 / v2 / v4 kernels of gemm16.hip, z: row-stationary, A..Z, 0..9: the LDS-DMA g5 kernels of
     gemm5.hip) at fp32 accuracy on ragged shapes (M, N, K not multiples of the tiles; K % 64
-    != 0, odd k32-step count; N = 3; K % 8 != 0 takes the register-staged fallback)."""
+    != 0, odd k32-step count; N = 3; K % 8 != 0, where a g5 letter runs the k-looped
+    dispatcher's own choice)."""
     from fgreg import linear as fl
     monkeypatch.setenv('FGR_GEMM16_TILE', tile)
     g = torch.Generator().manual_seed(11)

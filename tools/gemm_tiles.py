@@ -50,7 +50,7 @@ KSPLITS = ['']
 
 def main():
     global KSPLITS
-    cfgs = sys.argv[1] if len(sys.argv) > 1 else 'btukABCDEFGHIJ'
+    cfgs = sys.argv[1] if len(sys.argv) > 1 else 'efktuySTWXY'
     if 'ks' in sys.argv[2:]:
         KSPLITS = ['1', '2', '4', '8']
     bf = 'bf16' in sys.argv[2:]

@@ -13,12 +13,10 @@
 //
 // MFMA 16x16x4 f32 lane maps (lane l, g = l >> 4, c = l & 15):
 //   A[i = c][k = g], B[k = g][j = c], C/D[row = 4g + r][col = c], r = 0..3.
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kBQ = 64;   // query rows per block
 constexpr int kBK = 64;   // keys per tile

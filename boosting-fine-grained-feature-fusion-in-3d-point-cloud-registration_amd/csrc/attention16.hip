@@ -30,37 +30,14 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // 16-B units per (tile, head) image and the first V unit, by head dim
 template <int DH> constexpr int units() { return DH * 16 + (DH / 32) * 512; }
 template <int DH> constexpr int unit_v() { return (DH / 32) * 512; }
-
-__device__ __forceinline__ float xg_max16(float v) {   // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float xg_sum16(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// power-of-two exponent e with max * 2^e in [2^14, 2^15) (0 for an all-zero block)
-__device__ __forceinline__ int range_exp(float mx) {
-    return mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
-}
 
 __device__ __forceinline__ void split2(float x, _Float16& h, _Float16& m) {
     h = (_Float16)x;
@@ -122,7 +99,7 @@ __device__ __forceinline__ void kv_image16(const float* __restrict__ k, int64_t 
     __syncthreads();
     km = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
     vm = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-    const int ek = range_exp(km), ev = range_exp(vm);
+    const int ek = row_scale_exp(km), ev = row_scale_exp(vm);
     if (threadIdx.x == 0) sc[tile] = make_int2(ek, ev);
     const float sk = __builtin_ldexpf(1.f, ek), sv = __builtin_ldexpf(1.f, ev);
 #pragma unroll
@@ -178,11 +155,6 @@ __global__ void __launch_bounds__(256) attn_image16_jobs_kernel(ImgJobs j) {
                    j.img[job], j.sc[job], s, blockIdx.y, blockIdx.x, j.v_part[job] != 0);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0_a() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4));
-}
-
 // ---- key-tile loop: the K/V tile images go global -> LDS by LDS-DMA into two buffers (tile
 // t + 1 in flight while tile t is computed; one barrier per tile, no staging registers, no
 // ds_write pass); the per-tile scale exponents come by scalar loads (block-uniform address).
@@ -199,17 +171,7 @@ __device__ __forceinline__ void wait_vm_lgkm0_a() {
 //     instruction offsets (no per-tile address arithmetic), K/V DMA pieces contiguous per
 //     wave (one 64-bit add per tile, the pieces by instruction offsets);
 //   * built with -fno-slp-vectorize (packed fp32 VALU costs ~22 extra cycles beside MFMAs).
-// maxima of MFMA results: plain fmaxf (the file is built -fno-honor-nans, so no NaN
-// canonicalisation of the inputs; inline asm cannot be used here: the compiler's hazard
-// recognizer does not see an asm block's reads of MFMA results)
-__device__ __forceinline__ float vmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float vmax2(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ float xg_max16_nc(float v) {   // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = vmax2(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return vmax2(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
+// maxima of MFMA results: vmax2 / vmax3 (mfma.h; the file is built -fno-honor-nans)
 // x[0..7] (in fp16 range) -> h = f16(x) packed by v_cvt_pk_f16_f32 (RNE, the bits of split2's
 // hi), l = f16(x - h) by v_fma_mix (x - h exact in fp32, one rounding). Ends with `s_nop 1`:
 // the terms feed MFMAs (cdna_hip_programming.md 5.7 item 2).
@@ -298,7 +260,7 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
             x[kd][e] *= scale_log2;
             qm = fmaxf(qm, fabsf(x[kd][e]));
         }
-    const int eq = range_exp(xg_max16(qm));
+    const int eq = row_scale_exp(xg_max(qm));
     const float sq = __builtin_ldexpf(1.f, eq);
     f16x8 qt[KD][2];
 #pragma unroll
@@ -348,7 +310,7 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
     auto tile = [&](int tt, auto buf_tag, auto mask_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool MASK = decltype(mask_tag)::value;
-        wait_vm_lgkm0_a<0>();           // this wave's pieces of tile tt landed
+        wait_vm_lgkm0<0>();           // this wave's pieces of tile tt landed
         __builtin_amdgcn_s_barrier();   // everyone's landed; buffer 1 - BUF no longer read
         if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
         const int2 e2 = sc[tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head];
@@ -391,7 +353,7 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
         mx = vmax3(mx, s[2][3], s[3][0]);
         mx = vmax3(mx, s[3][1], s[3][2]);
         mx = vmax2(mx, s[3][3]);
-        mx = xg_max16_nc(mx) * f;
+        mx = xg_max(mx) * f;
         const float m_new = vmax2(m_run, mx);           // finite: every tile has a valid key
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
@@ -468,7 +430,7 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
     }
 
     // O^T (dh 16t + 4g + r, query c) / l (both in 2^14 units)
-    const float lsum = xg_sum16(l_run);
+    const float lsum = xg_sum(l_run);
     const float inv = (DROP ? inv_keep : 1.0f) / lsum;
     // training: the row's log2-sum-exp of the scaled scores (l in 2^14 units) for the
     // backward, which then skips its own first pass (fgr_attention_bwd_train)
@@ -555,7 +517,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
         dpart += ((da.x * oa.x + da.y * oa.y) + (da.z * oa.z + da.w * oa.w)) +
                  ((db.x * ob.x + db.y * ob.y) + (db.z * ob.z + db.w * ob.w));
     }
-    const float D = xg_sum16(dpart);
+    const float D = xg_sum(dpart);
     const float lse2 = qok ? lse_in[qrow * n_head + head] : 0.f;
     float qm = 0.f, dm = 0.f;
 #pragma unroll
@@ -566,7 +528,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
             qm = fmaxf(qm, fabsf(x[kd][e]));
             dm = fmaxf(dm, fabsf(y[kd][e]));
         }
-    const int eq = range_exp(xg_max16(qm)), edo = range_exp(xg_max16(dm));
+    const int eq = row_scale_exp(xg_max(qm)), edo = row_scale_exp(xg_max(dm));
     const float sq = __builtin_ldexpf(1.f, eq), sdo = __builtin_ldexpf(1.f, edo);
     f16x8 qt[KD][2], dt[KD][2];
 #pragma unroll
@@ -610,7 +572,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
 
     auto tile = [&](int tt, auto buf_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
-        wait_vm_lgkm0_a<0>();
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
         const int2 ek2 = sck[tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head];
@@ -661,7 +623,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
                 dmx = fmaxf(dmx, fabsf(v));
             }
         // per (query, tile) power of two bringing dS into fp16's range
-        const int eds = range_exp(xg_max16(dmx));
+        const int eds = row_scale_exp(xg_max(dmx));
         const float sds = __builtin_ldexpf(1.f, eds);
         f32x4 tmp[TD];
 #pragma unroll
@@ -790,7 +752,7 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
             vm = fmaxf(vm, fabsf(y[kd][e]));
         }
     }
-    const int ek = range_exp(xg_max16(km)), ev = range_exp(xg_max16(vm));
+    const int ek = row_scale_exp(xg_max(km)), ev = row_scale_exp(xg_max(vm));
     const float sk = __builtin_ldexpf(1.f, ek), sv = __builtin_ldexpf(1.f, ev);
     f16x8 kt[KD][2], vt[KD][2];
 #pragma unroll
@@ -850,7 +812,7 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
 
         auto tile = [&](int tt, auto buf_tag) {
             constexpr int BUF = decltype(buf_tag)::value;
-            wait_vm_lgkm0_a<0>();
+            wait_vm_lgkm0<0>();
             __builtin_amdgcn_s_barrier();
             if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
             const int64_t ti = tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head;
@@ -903,7 +865,7 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
                     dmx = fmaxf(dmx, fabsf(d));
                 }
             }
-            const int eds = range_exp(xg_max16(dmx));
+            const int eds = row_scale_exp(xg_max(dmx));
             const float sds = __builtin_ldexpf(1.f, eds);
             f32x4 tv[TD], tk[TD];
 #pragma unroll

@@ -20,25 +20,10 @@
 #include <cstring>
 #include <type_traits>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float finish_bf(float y, float b, float r, int act) {
-    if (act == FGR_ACT_RELU_RES_LEAKY) {
-        const float t = fmaxf(y + b, 0.f) + r;
-        return t > 0.f ? t : 0.1f * t;
-    }
-    const float t = y + b + r;
-    return act == FGR_ACT_RELU ? fmaxf(t, 0.f) : t;
-}
 
 __global__ void split_weights_bf16_kernel(const float* __restrict__ w, int n, int k, int64_t sn,
                                           int64_t sk, int ksteps, u32x4* __restrict__ img) {
@@ -241,13 +226,13 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
                 if (p.bias) bb = *reinterpret_cast<const float4*>(p.bias + n);
                 if (rrow) rr = *reinterpret_cast<const float4*>(rrow + n);
                 *reinterpret_cast<float4*>(crow + n) = make_float4(
-                    finish_bf(acc[j][i][0], bb.x, rr.x, p.act), finish_bf(acc[j][i][1], bb.y, rr.y, p.act),
-                    finish_bf(acc[j][i][2], bb.z, rr.z, p.act), finish_bf(acc[j][i][3], bb.w, rr.w, p.act));
+                    finish_out(acc[j][i][0], bb.x, rr.x, p.act), finish_out(acc[j][i][1], bb.y, rr.y, p.act),
+                    finish_out(acc[j][i][2], bb.z, rr.z, p.act), finish_out(acc[j][i][3], bb.w, rr.w, p.act));
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (n + e >= p.N) break;
-                    crow[n + e] = finish_bf(acc[j][i][e], p.bias ? p.bias[n + e] : 0.f,
+                    crow[n + e] = finish_out(acc[j][i][e], p.bias ? p.bias[n + e] : 0.f,
                                             rrow ? rrow[n + e] : 0.f, p.act);
                 }
             }
@@ -256,19 +241,6 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
 }
 
 // ---------------------------------- attention ------------------------------------------
-__device__ __forceinline__ float xg_max16b(float v) {   // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float xg_sum16b(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 // 16-B units per (tile, head) image and the first V unit
 template <int DH> constexpr int bf_units() { return DH * 8 + (DH / 32) * 256; }
 template <int DH> constexpr int bf_unit_v() { return (DH / 32) * 256; }
@@ -317,9 +289,7 @@ attn_kv_image_bf16_kernel(const float* __restrict__ k, int64_t ld_k, const float
 // canonicalisation, the tile loop unrolled by two so both LDS buffers' addresses are per-lane
 // constants + instruction offsets, DMA pieces contiguous per wave; built -fno-slp-vectorize.
 // The round-2 loop issued ~14 VALU per MFMA at head dim 32 (profiles/r03_pmc_attn_v1_before.json).
-// (plain fmaxf: the file is built -fno-honor-nans; see attention16.hip)
-__device__ __forceinline__ float vmax3b(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float vmax2b(float a, float b) { return fmaxf(a, b); }
+// (vmax2 / vmax3, mfma.h: plain fmaxf, the file is built -fno-honor-nans)
 
 template <int DH>
 __global__ void __launch_bounds__(256, 4)
@@ -399,7 +369,7 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
     auto tile = [&](int tt, auto buf_tag, auto mask_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool MASK = decltype(mask_tag)::value;
-        __builtin_amdgcn_s_waitcnt((7 << 4));                    // vmcnt(0) lgkmcnt(0)
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
         lds_c* const bp = (lds_c*)(BUF == 0 ? lds_b0 : lds_b1);
@@ -426,21 +396,15 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
                     if (kl < lo || kl >= hi) s[n][r] = -INFINITY;
                 }
         }
-        float mx = vmax3b(s[0][0], s[0][1], s[0][2]);
-        mx = vmax3b(mx, s[0][3], s[1][0]);
-        mx = vmax3b(mx, s[1][1], s[1][2]);
-        mx = vmax3b(mx, s[1][3], s[2][0]);
-        mx = vmax3b(mx, s[2][1], s[2][2]);
-        mx = vmax3b(mx, s[2][3], s[3][0]);
-        mx = vmax3b(mx, s[3][1], s[3][2]);
-        mx = vmax2b(mx, s[3][3]);
-        {
-            auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = vmax2b(__uint_as_float(a[0]), __uint_as_float(a[1]));
-            auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = vmax2b(__uint_as_float(b[0]), __uint_as_float(b[1]));
-        }
-        const float m_new = vmax2b(m_run, mx);
+        float mx = vmax3(s[0][0], s[0][1], s[0][2]);
+        mx = vmax3(mx, s[0][3], s[1][0]);
+        mx = vmax3(mx, s[1][1], s[1][2]);
+        mx = vmax3(mx, s[1][3], s[2][0]);
+        mx = vmax3(mx, s[2][1], s[2][2]);
+        mx = vmax3(mx, s[2][3], s[3][0]);
+        mx = vmax3(mx, s[3][1], s[3][2]);
+        mx = xg_max(vmax2(mx, s[3][3]));
+        const float m_new = vmax2(m_run, mx);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
         float rs = 0.f;
@@ -493,7 +457,7 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
         if ((tt + shift) & 1) tile(tt, B1{}, std::true_type{});
         else tile(tt, B0{}, std::true_type{});
     }
-    const float inv = 1.0f / xg_sum16b(l_run);
+    const float inv = 1.0f / xg_sum(l_run);
     if (qrow < qe) {
 #pragma unroll
         for (int t = 0; t < TD; ++t) {
@@ -510,14 +474,6 @@ size_t image_bytes_bf(int n, int k) { return (size_t)((n + 15) / 16) * ksteps_bf
 int64_t n_tiles_bf(int64_t n_kv_rows, int32_t n_kv_seg) { return n_kv_rows / 64 + n_kv_seg + 1; }
 
 }  // namespace
-bool gemm_g5_bf16(char cfg, const float* A, int64_t lda, const void* W, int ksteps, float* C,
-                  int64_t ldc, const float* bias, const float* R, int64_t ldr, int M, int N, int K,
-                  int act, int vec_out, hipStream_t st, int ksplit, float* part);
-bool g5_tile(char cfg, int* bm, int* bn);
-int g5_ksplit(int M, int N, int K, int BM, int BN);
-inline bool splitk_shape(int m, int n, int k) {        // as gemm16.hip
-    return k >= 1920 && n <= 256 && (int64_t)((m + 63) / 64) * ((n + 63) / 64) <= 160;
-}
 
 // narrow outputs with long contractions: the 64 x 64 LDS-DMA g5 ('X', gemm5.hip; measured
 // 1.2-1.5x faster there); few tiles (<= 400 of 64 x 64) with K >= 512 and the short-M

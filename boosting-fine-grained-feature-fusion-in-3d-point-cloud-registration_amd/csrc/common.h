@@ -94,16 +94,6 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += dpp<0x140>(v);
     return v;
 }
-// Sum over all 64 lanes without the LDS crossbar: DPP within each 16-lane row, then
-// v_permlane16/32_swap across the four rows; every lane gets the total.
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-    v = row16_sum(v);
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 // Index of the segment containing row r, given sorted offsets off[0..n] (off[0] = 0).
 __device__ __forceinline__ int find_segment(const int64_t* off, int n, int64_t r) {
     int lo = 0, hi = n - 1;
@@ -112,6 +102,15 @@ __device__ __forceinline__ int find_segment(const int64_t* off, int n, int64_t r
         if (off[mid] <= r) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// KPConv kernel-point influence of a neighbour at (nx, ny, nz): linear in its distance to
+// kernel point k, zero beyond the extent (the forward and its backward)
+__device__ __forceinline__ float kp_weight(float nx, float ny, float nz, const float* kp, int k,
+                                           float inv_extent) {
+    float dx = nx - kp[3 * k], dy = ny - kp[3 * k + 1], dz = nz - kp[3 * k + 2];
+    float d2 = dx * dx + dy * dy + dz * dz;
+    return fmaxf(1.0f - sqrtf(d2) * inv_extent, 0.0f);
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -174,6 +173,52 @@ __device__ __forceinline__ uint32_t attn_drop_hash(uint32_t seed, int head, int6
     x = (x ^ (x >> 15)) * 0x846CA68Bu;
     return x ^ (x >> 16);
 }
+
+// ---- functions, structs and constants that one .hip file defines and another uses: declared
+// here only (default arguments included), and every defining file includes this header, so the
+// compiler checks each definition against its declaration.
+
+// few 64 x 64 tiles, narrow output, long contraction: split-K pays (measured)
+inline bool splitk_shape(int m, int n, int k) {
+    return k >= 1920 && n <= 256 && (int64_t)((m + 63) / 64) * ((n + 63) / 64) <= 160;
+}
+
+// gemm5.hip: the LDS-DMA "g5" GEMMs. A 16-B aligned with lda % 4 == 0 and K % 8 == 0 (checked
+// by the callers). ksplit > 1: split-K over ksplit parts with `part` = ksplit * M * N floats
+bool gemm_g5_f16x3(char cfg, const float* A, int64_t lda, const void* W, int ksteps,
+                   const float* wsc, float* C, int64_t ldc, const float* bias, const float* R,
+                   int64_t ldr, int M, int N, int K, int act, int vec_out, hipStream_t st,
+                   int ksplit, float* part);
+bool gemm_g5_f16x3_qkv(const float* A, int64_t lda, const void* W, int ksteps, const float* wsc,
+                       float* q, int64_t ld_q, const float* bias, int M, int d, int n_head,
+                       char* kv_img, int2* kv_sc, hipStream_t st);
+bool gemm_g5_bf16(char cfg, const float* A, int64_t lda, const void* W, int ksteps, float* C,
+                  int64_t ldc, const float* bias, const float* R, int64_t ldr, int M, int N, int K,
+                  int act, int vec_out, hipStream_t st, int ksplit, float* part);
+bool g5_tile(char cfg, int* bm, int* bn);                // tile of a g5 variant, false if unknown
+int g5_ksplit(int M, int N, int K, int BM, int BN);      // split-K factor on BM x BN tiles
+
+// bf16.hip: the bf16 GEMM's tile letters and dispatch
+extern const char kBf16Tiles[];
+char bf16_tile(int m, int n, int k);
+int bf16_ksplit(char cfg, int m, int n, int k);
+
+// gemm_rs.hip: the row-stationary f16x3 GEMM (K <= 256). `ln` (optional, no R): the LayerNorm
+// prologue's gamma, beta, add (16-B aligned rows), ld_add and eps
+struct RsLn {
+    const float* g; const float* b; const float* add; int64_t ld_add; float eps;
+    const float* g2; const float* b2; float* out2; int64_t ld_out2;    // optional side output
+    char* kv_img; int2* kv_sc; int n_head; int kv_col0;                // optional K / V images
+};
+// the correspondence-head epilogues (see the top of gemm_rs.hip): n_act / c2, or out3 with w4 / b4
+struct RsHead {
+    int n_act; float* c2;
+    const float* w4; const float* b4; float* out3;
+};
+bool gemm_rs_f16x3(const float* A, int64_t lda, const void* W, int ksteps, const float* wsc,
+                   float* C, int64_t ldc, const float* bias, const float* R, int64_t ldr, int M,
+                   int N, int K, int act, hipStream_t st, const RsLn* ln = nullptr,
+                   const RsHead* head = nullptr);
 
 // attention16.hip: the training attention backward on the f16 matrix cores (fgr_attention_bwd_train)
 size_t attn_bwd_f16x3_bytes(int64_t n_rows, int32_t n_seg, int32_t n_head, int32_t dh);

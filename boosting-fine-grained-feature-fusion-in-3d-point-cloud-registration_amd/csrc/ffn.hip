@@ -49,7 +49,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "mfma.h"
 
 #ifdef FGR_FFN_STAMP
 // Diagnostic build only (tools/ffn_stamp.py): per (block, wave) cycle sums of the loop's phases
@@ -63,9 +63,6 @@ __device__ unsigned long long g_ffn_stamp[4096][4][8];
 
 namespace fgr {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kFfnD = 256;                  // d_model
 constexpr int kFfnKS = kFfnD / 32;          // k32 steps of linear1 (8)
@@ -86,37 +83,18 @@ struct FfnArgs {
     int M, F;
 };
 
-// s_waitcnt vmcnt(N) lgkmcnt(0) (gfx9 encoding)
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0_f() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4));
-}
 // vmcnt(4 n) lgkmcnt(0) for a wave-uniform n in [0, kRing - 2]
 __device__ __forceinline__ void wait_units(int n) {
     static_assert(kRing - 2 <= 6, "extend the switch");
     switch (n) {
-        case 0: wait_vm_lgkm0_f<0>(); break;
-        case 1: wait_vm_lgkm0_f<4>(); break;
-        case 2: wait_vm_lgkm0_f<8>(); break;
-        case 3: wait_vm_lgkm0_f<12>(); break;
-        case 4: wait_vm_lgkm0_f<16>(); break;
-        case 5: wait_vm_lgkm0_f<20>(); break;
-        default: wait_vm_lgkm0_f<24>(); break;
+        case 0: wait_vm_lgkm0<0>(); break;
+        case 1: wait_vm_lgkm0<4>(); break;
+        case 2: wait_vm_lgkm0<8>(); break;
+        case 3: wait_vm_lgkm0<12>(); break;
+        case 4: wait_vm_lgkm0<16>(); break;
+        case 5: wait_vm_lgkm0<20>(); break;
+        default: wait_vm_lgkm0<24>(); break;
     }
-}
-
-__device__ __forceinline__ float xg_sum_f(float v) {      // sum over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-__device__ __forceinline__ float xg_max_f(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 
 typedef __attribute__((address_space(3))) u32x4 lds_u4;
@@ -251,11 +229,11 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
     for (int u = 0; u < kRing; ++u) dma(u, u);         // nu >= 8 (f >= 64: supported())
     // the row and parameter loads are older than the DMA pieces: vmcnt(4 kRing) leaves the
     // pieces in flight
-    wait_vm_lgkm0_f<4 * kRing>();
+    wait_vm_lgkm0<4 * kRing>();
     if (tid < nf4) { cw1[tid] = pw1a; cb1[tid] = pb1a; }
     if (tid + 256 < nf4) { cw1[tid + 256] = pw1b; cb1[tid + 256] = pb1b; }
     if (tid < kFfnD / 4) { cw2[tid] = pw2; cb2[tid] = pb2; lng[tid] = pg; lnb[tid] = pbe; }
-    wait_vm_lgkm0_f<4 * kRing - 4>();     // the LDS writes (lgkmcnt 0) and unit 0's pieces
+    wait_vm_lgkm0<4 * kRing - 4>();     // the LDS writes (lgkmcnt 0) and unit 0's pieces
     __builtin_amdgcn_s_barrier();
     const int lane_u = g * 16 + c;
     u32x4 wa[16], wb[16];                 // fragment double buffer: units of even / odd index
@@ -270,7 +248,7 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
         for (int s = 0; s < kFfnKS; ++s)
             sm += ((xr[s][0] + xr[s][1]) + (xr[s][2] + xr[s][3])) +
                   ((xr[s][4] + xr[s][5]) + (xr[s][6] + xr[s][7]));
-        const float mean = xg_sum_f(sm) / (float)kFfnD;
+        const float mean = xg_sum(sm) / (float)kFfnD;
         float sq = 0.f;
 #pragma unroll
         for (int s = 0; s < kFfnKS; ++s)
@@ -279,7 +257,7 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
                 const float d = xr[s][e] - mean;
                 sq += d * d;
             }
-        const float rstd = 1.0f / sqrtf(xg_sum_f(sq) / (float)kFfnD + p.eps);
+        const float rstd = 1.0f / sqrtf(xg_sum(sq) / (float)kFfnD + p.eps);
         float mx = 0.f, nn = 0.f;
 #pragma unroll
         for (int s = 0; s < kFfnKS; ++s) {
@@ -298,9 +276,9 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
             mx = fmaxf(mx, max3_abs(xr[s][3], xr[s][4], xr[s][5]));
             mx = fmaxf(mx, max3_abs(xr[s][6], xr[s][7], 0.f));
         }
-        mx = xg_max_f(mx);
-        nn = xg_sum_f(nn);
-        const int ea = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+        mx = xg_max(mx);
+        nn = xg_sum(nn);
+        const int ea = row_scale_exp(mx);
         const float sca = __builtin_ldexpf(1.f, ea);
 #pragma unroll
         for (int s = 0; s < kFfnKS; ++s) {
@@ -463,15 +441,12 @@ static_assert(kV2Groups % kV2Ring == 0, "ring slot = group index mod kV2Ring at 
 
 // s_waitcnt vmcnt(n) (lgkmcnt / expcnt untouched) for n = 4 k <= 28
 __device__ __forceinline__ void wait_vm_only(int n) {
-    // vmcnt field bits 3:0 and 15:14, expcnt 6:4 = 7, lgkmcnt 11:8 = 15 (no wait)
-#define FGR_VMW(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | (7 << 4) | (15 << 8))
     switch (n) {
-        case 0: FGR_VMW(0); break;   case 4: FGR_VMW(4); break;
-        case 8: FGR_VMW(8); break;   case 12: FGR_VMW(12); break;
-        case 16: FGR_VMW(16); break; case 20: FGR_VMW(20); break;
-        case 24: FGR_VMW(24); break; default: FGR_VMW(28); break;
+        case 0: wait_vm<0>(); break;   case 4: wait_vm<4>(); break;
+        case 8: wait_vm<8>(); break;   case 12: wait_vm<12>(); break;
+        case 16: wait_vm<16>(); break; case 20: wait_vm<20>(); break;
+        case 24: wait_vm<24>(); break; default: wait_vm<28>(); break;
     }
-#undef FGR_VMW
 }
 
 // (S z) Phi(z) for sz = S z and isq = 1 / (S sqrt 2): the scaled GELU of a hidden value
@@ -570,7 +545,7 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
         for (int s = 0; s < kFfnKS; ++s)
             sm += ((xr[s][0] + xr[s][1]) + (xr[s][2] + xr[s][3])) +
                   ((xr[s][4] + xr[s][5]) + (xr[s][6] + xr[s][7]));
-        const float mean = xg_sum_f(sm) / (float)kFfnD;
+        const float mean = xg_sum(sm) / (float)kFfnD;
         float sq = 0.f;
 #pragma unroll
         for (int s = 0; s < kFfnKS; ++s)
@@ -579,7 +554,7 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
                 const float d = xr[s][e] - mean;
                 sq += d * d;
             }
-        const float rstd = 1.0f / sqrtf(xg_sum_f(sq) / (float)kFfnD + p.eps);
+        const float rstd = 1.0f / sqrtf(xg_sum(sq) / (float)kFfnD + p.eps);
         float mx = 0.f, nn = 0.f;
 #pragma unroll
         for (int s = 0; s < kFfnKS; ++s) {
@@ -598,9 +573,9 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
             mx = fmaxf(mx, max3_abs(xr[s][3], xr[s][4], xr[s][5]));
             mx = fmaxf(mx, max3_abs(xr[s][6], xr[s][7], 0.f));
         }
-        mx = xg_max_f(mx);
-        nn = xg_sum_f(nn);
-        const int ea = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+        mx = xg_max(mx);
+        nn = xg_sum(nn);
+        const int ea = row_scale_exp(mx);
         const float sca = __builtin_ldexpf(1.f, ea);
         if (wv < RT) {
 #pragma unroll
@@ -735,7 +710,7 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
                     }
                     // every wave's chunk in LDS (and every wave done with the buffer's previous
                     // use, step st - 2, which ended before its barrier of step st - 1)
-                    __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));   // lgkmcnt(0)
+                    wait_lgkm0();   // lgkmcnt(0)
                     __builtin_amdgcn_s_barrier();
                     read_h(st & 1, 0, fa[0]);
                 }
@@ -811,7 +786,7 @@ ffn_w2_split_kernel(const float* __restrict__ w, int n, int f, int64_t sn, int64
         float m = 0.f;
 #pragma unroll
         for (int z = 0; z < 16; ++z) m = fmaxf(m, red[tid][z]);
-        const int e = m > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(m), 127) : 0;
+        const int e = row_scale_exp(m);
         const bool ok = r0 + tid < n;
         scale_inv[tid] = ok ? __builtin_ldexpf(1.f, e) : 0.f;
         wsc[r0 + tid] = ok ? __builtin_ldexpf(1.f, -e) : 0.f;

@@ -31,43 +31,10 @@
 // B[k = 8g + e][j = c], C[i = 4g + r][j = c].
 #include <cstring>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
-bool gemm_g5_f16x3(char cfg, const float* A, int64_t lda, const void* W, int ksteps,
-                   const float* wsc, float* C, int64_t ldc, const float* bias, const float* R,
-                   int64_t ldr, int M, int N, int K, int act, int vec_out, hipStream_t st,
-                   int ksplit, float* part);
-bool g5_tile(char cfg, int* bm, int* bn);
-bool gemm_g5_f16x3_qkv(const float* A, int64_t lda, const void* W, int ksteps, const float* wsc,
-                       float* q, int64_t ld_q, const float* bias, int M, int d, int n_head,
-                       char* kv_img, int2* kv_sc, hipStream_t st);
-int g5_ksplit(int M, int N, int K, int BM, int BN);
-char bf16_tile(int m, int n, int k);
-extern const char kBf16Tiles[];
-int bf16_ksplit(char cfg, int m, int n, int k);
-struct RsLn {
-    const float* g; const float* b; const float* add; int64_t ld_add; float eps;
-    const float* g2; const float* b2; float* out2; int64_t ld_out2;    // optional side output
-    char* kv_img; int2* kv_sc; int n_head; int kv_col0;                // optional K / V images
-};
-struct RsHead {
-    int n_act; float* c2;
-    const float* w4; const float* b4; float* out3;
-};
-bool gemm_rs_f16x3(const float* A, int64_t lda, const void* W, int ksteps, const float* wsc,
-                   float* C, int64_t ldc, const float* bias, const float* R, int64_t ldr, int M,
-                   int N, int K, int act, hipStream_t st, const RsLn* ln = nullptr,
-                   const RsHead* head = nullptr);
-// few 64 x 64 tiles, narrow output, long contraction: split-K pays (measured)
-inline bool splitk_shape(int m, int n, int k) {
-    return k >= 1920 && n <= 256 && (int64_t)((m + 63) / 64) * ((n + 63) / 64) <= 160;
-}
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SH_UNSET = 0x3fff;     // "no non-zero chunk seen yet" (partial sums are 0)
 
@@ -80,40 +47,6 @@ struct GemmH3Args {
     const float* R; int64_t ldr;
     int M, N, K, act, vec_out;
 };
-
-__device__ __forceinline__ float xg_max16(float v) {   // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float xg_sum16(float v) {   // sum over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-
-// scale exponent for a chunk whose max |x| is cm: cm * 2^sh in [2^7, 2^8)
-__device__ __forceinline__ int chunk_shift(float cm) {
-    return min(8 - __builtin_amdgcn_frexp_expf(cm), 127);
-}
-
-// Epilogue of one output: act(y + b + r), or LeakyReLU_0.1(ReLU(y + b) + r) for
-// FGR_ACT_RELU_RES_LEAKY (absent bias / residual come in as 0).
-__device__ __forceinline__ float finish_out(float y, float b, float r, int act) {
-    if (act == FGR_ACT_RELU_RES_LEAKY) {
-        const float t = fmaxf(y + b, 0.f) + r;
-        return t > 0.f ? t : 0.1f * t;
-    }
-    const float t = y + b + r;
-    return act == FGR_ACT_RELU ? fmaxf(t, 0.f) : t;
-}
 
 // Stores one lane's 4 consecutive outputs n..n+3 of a row (16-B accesses when vec and the
 // 4 columns are in range).
@@ -220,8 +153,8 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
                                 ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
             float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
             cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dppf<0xB1>(cm));              // the row's 4 lanes: quad xor 1, xor 2
-            cm = fmaxf(cm, dppf<0x4E>(cm));
+            cm = fmaxf(cm, dpp<0xB1>(cm));              // the row's 4 lanes: quad xor 1, xor 2
+            cm = fmaxf(cm, dpp<0x4E>(cm));
             if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
             const float s = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
             f16x8 th, tm;
@@ -429,9 +362,9 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
                                 ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
             float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
             cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dppf<0xB1>(cm));              // the row's lanes: quad xor 1, xor 2,
-            cm = fmaxf(cm, dppf<0x4E>(cm));
-            if constexpr (RU == 8) cm = fmaxf(cm, dppf<0x141>(cm));   // + half-row mirror
+            cm = fmaxf(cm, dpp<0xB1>(cm));              // the row's lanes: quad xor 1, xor 2,
+            cm = fmaxf(cm, dpp<0x4E>(cm));
+            if constexpr (RU == 8) cm = fmaxf(cm, dpp<0x141>(cm));   // + half-row mirror
             if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
             const float s = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
             f16x8 th, tm;
@@ -626,8 +559,8 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
                                 ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
             float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
             cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dppf<0xB1>(cm));
-            cm = fmaxf(cm, dppf<0x4E>(cm));
+            cm = fmaxf(cm, dpp<0xB1>(cm));
+            cm = fmaxf(cm, dpp<0x4E>(cm));
             if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
             const float sc = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
             f16x8 th, tm;
@@ -766,7 +699,7 @@ __global__ void weight_scale_kernel(const float* __restrict__ w, int n, int k, i
     }
     mx = wave_max(mx);
     if (lane == 0) {
-        const int e = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+        const int e = row_scale_exp(mx);
         wsc[row] = row < n ? __builtin_ldexpf(1.f, -e) : 0.f;
     }
 }
@@ -805,7 +738,7 @@ __global__ void weight_scale_finish(int n, int npad, float* __restrict__ wsc) {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= npad) return;
     const float mx = __uint_as_float(reinterpret_cast<const unsigned*>(wsc)[row]);
-    const int e = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+    const int e = row_scale_exp(mx);
     wsc[row] = row < n ? __builtin_ldexpf(1.f, -e) : 0.f;
 }
 
@@ -874,7 +807,7 @@ __device__ __forceinline__ void split_panel_h3(const float* __restrict__ w, int 
         float m = 0.f;
 #pragma unroll
         for (int q = 0; q < 16; ++q) m = fmaxf(m, red[tid][q]);
-        const int e = m > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(m), 127) : 0;
+        const int e = row_scale_exp(m);
         const bool ok = r0 + tid < n;
         scale_inv[tid] = ok ? __builtin_ldexpf(1.f, e) : 0.f;
         wsc[r0 + tid] = ok ? __builtin_ldexpf(1.f, -e) : 0.f;

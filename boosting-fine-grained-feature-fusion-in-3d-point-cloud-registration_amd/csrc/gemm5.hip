@@ -28,15 +28,11 @@
 // significant products hh, hm, mh in fp32 accumulation).
 // Lane maps of v_mfma_f32_16x16x32_{f16,bf16} (lane l, g = l >> 4, c = l & 15): A[i = c][k =
 // 8g + e], B[k = 8g + e][j = c], C[i = 4g + r][j = c].
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int SH_UNSET = 0x3fff;
@@ -69,34 +65,6 @@ constexpr int kKv64UnitV = 1024;
 // chunk swizzle of A row r (16-B chunk q of a 128-B row line lands at q ^ swz(r)): rows
 // {0-3, 12-15} and {4-11} of one ds_read_b128 lane group hit 16 distinct 16-B bank slots
 __device__ __forceinline__ int swz(int r) { return (r >> 1) & 5; }
-
-// s_waitcnt vmcnt(n) (expcnt / lgkmcnt: no wait) -- gfx9 encoding
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-// s_waitcnt vmcnt(n) lgkmcnt(0)
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4));
-}
-
-__device__ __forceinline__ float xg_max(float v) {        // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
-__device__ __forceinline__ float finish5(float y, float b, float r, int act) {
-    if (act == FGR_ACT_RELU_RES_LEAKY) {
-        const float t = fmaxf(y + b, 0.f) + r;
-        return t > 0.f ? t : 0.1f * t;
-    }
-    const float t = y + b + r;
-    return act == FGR_ACT_RELU ? fmaxf(t, 0.f) : t;
-}
 
 // TERMS 2: f16x3 (W image with hi / lo terms + row scales); 1: bf16 (single-term image).
 // KW k-groups of 4 waves (intra-block split-K): group h computes the k32-steps ks = h, h + KW,
@@ -252,7 +220,7 @@ __global__ void __launch_bounds__(256 * KW) gemm_g5(G5Args p) {
                 if (__builtin_amdgcn_ballot_w64(may)) {
                     cm = xg_max(cm);
                     const bool lower = cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[i] > 15;
-                    const int nsh = lower ? min(8 - __builtin_amdgcn_frexp_expf(cm), 127) : sh[i];
+                    const int nsh = lower ? chunk_shift(cm) : sh[i];
                     const float f = (sh[i] == SH_UNSET || !lower) ? 1.f
                                                                    : __builtin_ldexpf(1.f, nsh - sh[i]);
 #pragma unroll
@@ -513,7 +481,7 @@ __global__ void __launch_bounds__(256 * KW) gemm_g5(G5Args p) {
                         const int hh = item >> 9, key = (item >> 3) & 63, gg = item & 7;
                         const float tm = fmaxf(fmaxf(kvred[hh][0], kvred[hh][1]),
                                                fmaxf(kvred[hh][2], kvred[hh][3]));
-                        const int e = tm > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(tm), 127) : 0;
+                        const int e = row_scale_exp(tm);
                         const float sc = __builtin_ldexpf(1.f, e);
                         const int64_t ti = (int64_t)bm * p.n_head + head0 + hh;
                         if (tid == 0 && it == 0) reinterpret_cast<int*>(p.kv_sc + ti)[isv] = e;
@@ -558,14 +526,14 @@ __global__ void __launch_bounds__(256 * KW) gemm_g5(G5Args p) {
                     if (p.bias) bb = *reinterpret_cast<const float4*>(p.bias + n);
                     if (rrow) rr = *reinterpret_cast<const float4*>(rrow + n);
                     *reinterpret_cast<float4*>(crow + n) =
-                        make_float4(finish5(y.x, bb.x, rr.x, p.act), finish5(y.y, bb.y, rr.y, p.act),
-                                    finish5(y.z, bb.z, rr.z, p.act), finish5(y.w, bb.w, rr.w, p.act));
+                        make_float4(finish_out(y.x, bb.x, rr.x, p.act), finish_out(y.y, bb.y, rr.y, p.act),
+                                    finish_out(y.z, bb.z, rr.z, p.act), finish_out(y.w, bb.w, rr.w, p.act));
                 } else {
                     const float yv[4] = {y.x, y.y, y.z, y.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         if (n + e >= p.N) break;
-                        crow[n + e] = finish5(yv[e], p.bias ? p.bias[n + e] : 0.f,
+                        crow[n + e] = finish_out(yv[e], p.bias ? p.bias[n + e] : 0.f,
                                               rrow ? rrow[n + e] : 0.f, p.act);
                     }
                 }
@@ -595,13 +563,13 @@ __global__ void __launch_bounds__(256 * KW) gemm_g5(G5Args p) {
                 if (p.bias) bb = *reinterpret_cast<const float4*>(p.bias + n);
                 if (rrow) rr = *reinterpret_cast<const float4*>(rrow + n);
                 *reinterpret_cast<float4*>(crow + n) =
-                    make_float4(finish5(y[0], bb.x, rr.x, p.act), finish5(y[1], bb.y, rr.y, p.act),
-                                finish5(y[2], bb.z, rr.z, p.act), finish5(y[3], bb.w, rr.w, p.act));
+                    make_float4(finish_out(y[0], bb.x, rr.x, p.act), finish_out(y[1], bb.y, rr.y, p.act),
+                                finish_out(y[2], bb.z, rr.z, p.act), finish_out(y[3], bb.w, rr.w, p.act));
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (n + e >= p.N) break;
-                    crow[n + e] = finish5(y[e], p.bias ? p.bias[n + e] : 0.f,
+                    crow[n + e] = finish_out(y[e], p.bias ? p.bias[n + e] : 0.f,
                                           rrow ? rrow[n + e] : 0.f, p.act);
                 }
             }
@@ -638,14 +606,14 @@ __global__ void __launch_bounds__(256) g5_splitk_reduce(G5Args p) {
         if (p.bias) bb = *reinterpret_cast<const float4*>(p.bias + n);
         if (rrow) rr = *reinterpret_cast<const float4*>(rrow + n);
         *reinterpret_cast<float4*>(crow + n) =
-            make_float4(finish5(y.x, bb.x, rr.x, p.act), finish5(y.y, bb.y, rr.y, p.act),
-                        finish5(y.z, bb.z, rr.z, p.act), finish5(y.w, bb.w, rr.w, p.act));
+            make_float4(finish_out(y.x, bb.x, rr.x, p.act), finish_out(y.y, bb.y, rr.y, p.act),
+                        finish_out(y.z, bb.z, rr.z, p.act), finish_out(y.w, bb.w, rr.w, p.act));
         return;
     }
     for (int e = 0; e < 4 && n + e < p.N; ++e) {
         float y = pp[e];
         for (int z = 1; z < p.ksplit; ++z) y += pp[z * mn + e];
-        crow[n + e] = finish5(y, p.bias ? p.bias[n + e] : 0.f, rrow ? rrow[n + e] : 0.f, p.act);
+        crow[n + e] = finish_out(y, p.bias ? p.bias[n + e] : 0.f, rrow ? rrow[n + e] : 0.f, p.act);
     }
 }
 

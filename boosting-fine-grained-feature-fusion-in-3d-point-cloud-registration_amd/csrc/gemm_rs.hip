@@ -53,7 +53,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "mfma.h"
 
 #ifdef FGR_RS_STAMP
 // Diagnostic build only (tools/build_stamp.sh, tools/rs_stamp.py): per-block clock stamps of
@@ -66,9 +66,6 @@ __device__ unsigned long long g_rs_stamp[1 << 14][8];
 
 namespace fgr {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct RsArgs {
     const float* A; int64_t lda;
@@ -93,37 +90,17 @@ struct RsArgs {
     int n_head, kv_col0;              //   heads (head dim 32); first K column (V: + 32 n_head)
 };
 
-// s_waitcnt vmcnt(n) lgkmcnt(0) -- gfx9 encoding
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0_rs() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4));
-}
-
-__device__ __forceinline__ float xg_max_rs(float v) {     // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float xg_sum_rs(float v) {     // sum over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 // vmcnt(n) lgkmcnt(0) for a wave-uniform runtime n <= 15 (s_waitcnt takes an immediate)
 __device__ __forceinline__ void wait_vm_lgkm0_dyn(int n) {
     switch (n) {
-        case 0: wait_vm_lgkm0_rs<0>(); break;   case 1: wait_vm_lgkm0_rs<1>(); break;
-        case 2: wait_vm_lgkm0_rs<2>(); break;   case 3: wait_vm_lgkm0_rs<3>(); break;
-        case 4: wait_vm_lgkm0_rs<4>(); break;   case 5: wait_vm_lgkm0_rs<5>(); break;
-        case 6: wait_vm_lgkm0_rs<6>(); break;   case 7: wait_vm_lgkm0_rs<7>(); break;
-        case 8: wait_vm_lgkm0_rs<8>(); break;   case 9: wait_vm_lgkm0_rs<9>(); break;
-        case 10: wait_vm_lgkm0_rs<10>(); break; case 11: wait_vm_lgkm0_rs<11>(); break;
-        case 12: wait_vm_lgkm0_rs<12>(); break; case 13: wait_vm_lgkm0_rs<13>(); break;
-        case 14: wait_vm_lgkm0_rs<14>(); break; default: wait_vm_lgkm0_rs<15>(); break;
+        case 0: wait_vm_lgkm0<0>(); break;   case 1: wait_vm_lgkm0<1>(); break;
+        case 2: wait_vm_lgkm0<2>(); break;   case 3: wait_vm_lgkm0<3>(); break;
+        case 4: wait_vm_lgkm0<4>(); break;   case 5: wait_vm_lgkm0<5>(); break;
+        case 6: wait_vm_lgkm0<6>(); break;   case 7: wait_vm_lgkm0<7>(); break;
+        case 8: wait_vm_lgkm0<8>(); break;   case 9: wait_vm_lgkm0<9>(); break;
+        case 10: wait_vm_lgkm0<10>(); break; case 11: wait_vm_lgkm0<11>(); break;
+        case 12: wait_vm_lgkm0<12>(); break; case 13: wait_vm_lgkm0<13>(); break;
+        case 14: wait_vm_lgkm0<14>(); break; default: wait_vm_lgkm0<15>(); break;
     }
 }
 
@@ -141,21 +118,6 @@ constexpr int kRsMaxNc = 32;       // panels per block (the per-block column sca
 #define FGR_RS_LA 4
 #endif
 constexpr int kRsLookahead = FGR_RS_LA;   // k-steps of W fragments read ahead of their MFMAs
-
-// the epilogue of one output, the activation fixed at compile time
-template <int ACT, bool RES>
-__device__ __forceinline__ float finish_ct(float y, float b, float r) {
-    if constexpr (ACT == FGR_ACT_RELU_RES_LEAKY) {
-        float t = fmaxf(y + b, 0.f);
-        if constexpr (RES) t += r;
-        return t > 0.f ? t : 0.1f * t;
-    } else {
-        float t = y + b;
-        if constexpr (RES) t += r;
-        if constexpr (ACT == FGR_ACT_RELU) t = fmaxf(t, 0.f);
-        return t;
-    }
-}
 
 // LNM: 0 plain, 1 LayerNorm prologue, 2 LayerNorm prologue + row add, 3 as 2 plus a second
 // LayerNorm output of the same rows (the encoder's per-layer output norm), written by the
@@ -283,7 +245,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
             for (int s = 0; s < KS; ++s)
                 sm += ((x[s][0] + x[s][1]) + (x[s][2] + x[s][3])) +
                       ((x[s][4] + x[s][5]) + (x[s][6] + x[s][7]));
-            const float mean = xg_sum_rs(sm) / (float)p.K;
+            const float mean = xg_sum(sm) / (float)p.K;
             float sq = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
@@ -294,7 +256,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
                     sq += d * d;
                 }
             }
-            const float rstd = 1.0f / sqrtf(xg_sum_rs(sq) / (float)p.K + p.eps);
+            const float rstd = 1.0f / sqrtf(xg_sum(sq) / (float)p.K + p.eps);
             if constexpr (LNM == 3) {
                 // the side output first, fenced off from the add loads below (scheduled
                 // together they exceed the 256 registers of two waves per SIMD)
@@ -348,9 +310,9 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
             mx = fmaxf(mx, max3_abs(x[s][3], x[s][4], x[s][5]));
             mx = fmaxf(mx, max3_abs(x[s][6], x[s][7], 0.f));
         }
-        mx = xg_max_rs(mx);
+        mx = xg_max(mx);
         // max * 2^e in [2^14, 2^15) (e = 0 for an all-zero row)
-        const int e = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+        const int e = row_scale_exp(mx);
         rs[i] = __builtin_ldexpf(1.f, -e);
         const float sc = __builtin_ldexpf(1.f, e);
 #pragma unroll
@@ -385,7 +347,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
         const float tm = fmaxf(fmaxf(kvred[hd & 1][0], kvred[hd & 1][1]),
                                fmaxf(kvred[hd & 1][2], kvred[hd & 1][3]));
         const int isv = hd >= p.n_head ? 1 : 0, head = hd - isv * p.n_head;
-        const int e = tm > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(tm), 127) : 0;
+        const int e = row_scale_exp(tm);
         const float sc = __builtin_ldexpf(1.f, e);
         const int64_t tile = (int64_t)bm * p.n_head + head;
         if (tid == 0) reinterpret_cast<int*>(p.kv_sc + tile)[isv] = e;
@@ -510,7 +472,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
                 if (half == 0) {
                     kvm = mx;
                 } else {
-                    const float wm = xg_max_rs(row16_max(fmaxf(kvm, mx)));   // DPP + permlanes
+                    const float wm = xg_max(row16_max(fmaxf(kvm, mx)));   // DPP + permlanes
                     const int hd = rel >> 5;                    // head index over [K heads | V heads]
                     if (lane == 0) kvred[hd & 1][wv] = wm;
                     kv_pend = 1 + hd;                           // finalised after the next barrier
@@ -584,7 +546,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
             // q - 2)
             static_assert(PPS > 1 || LA == 2, "the wait counts below assume two panels in flight");
     #if defined(FGR_RS_WAIT0)
-            wait_vm_lgkm0_rs<0>();
+            wait_vm_lgkm0<0>();
     #else
             if (q == 0) wait_vm_lgkm0_dyn(np > 1 ? PW : 0);
             else wait_vm_lgkm0_dyn((q >= 3 ? nstore(q - 3) : 0) + (q >= 2 ? nstore(q - 2) : 0) +
@@ -710,7 +672,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
 #pragma unroll
         for (int i = 0; i < RT; ++i) {
             const int64_t row = mw + 16 * i + c;
-            const float t0 = xg_sum_rs(h3[i][0]), t1 = xg_sum_rs(h3[i][1]), t2 = xg_sum_rs(h3[i][2]);
+            const float t0 = xg_sum(h3[i][0]), t1 = xg_sum(h3[i][1]), t2 = xg_sum(h3[i][2]);
             if (g == 0 && row < p.M) {
                 p.out3[row * 3 + 0] = t0 + p.b4[0];
                 p.out3[row * 3 + 1] = t1 + p.b4[1];
@@ -771,18 +733,7 @@ bool launch_rs_k(const RsArgs& a, unsigned blocks, hipStream_t st) {
 }  // namespace
 
 // The rs kernel applies to K <= 256, K % 8 == 0, N % 16 == 0 with 16-B aligned A / C / R / bias rows
-// (checked by the caller). ksteps = the image's k32-steps (even, <= 8). `ln` (optional, no R):
-// the LayerNorm prologue's gamma, beta, add (16-B aligned rows), ld_add and eps.
-struct RsLn {
-    const float* g; const float* b; const float* add; int64_t ld_add; float eps;
-    const float* g2; const float* b2; float* out2; int64_t ld_out2;    // optional side output
-    char* kv_img; int2* kv_sc; int n_head; int kv_col0;                // optional K / V images
-};
-// the correspondence-head epilogues (see the top of this file): n_act / c2, or out3 with w4 / b4
-struct RsHead {
-    int n_act; float* c2;
-    const float* w4; const float* b4; float* out3;
-};
+// (checked by the caller). ksteps = the image's k32-steps (even, <= 8). RsLn / RsHead: common.h.
 bool gemm_rs_f16x3(const float* A, int64_t lda, const void* W, int ksteps, const float* wsc,
                    float* C, int64_t ldc, const float* bias, const float* R, int64_t ldr, int M,
                    int N, int K, int act, hipStream_t st, const RsLn* ln, const RsHead* head) {

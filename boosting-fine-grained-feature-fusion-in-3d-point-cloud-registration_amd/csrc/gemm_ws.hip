@@ -27,7 +27,7 @@
 // v_swz chunk swizzle) with 8-B stores (4 dims x fp16 per lane and term).
 //
 // Precision: as gemm_rs.hip (one scale per activation row, three fp16 products per product).
-#include "common.h"
+#include "mfma.h"
 
 #ifdef FGR_WS_STAMP
 // Diagnostic build only (tools/ws_bench.py): per (block, wave) s_memtime stamps: [0] entry,
@@ -38,9 +38,6 @@ __device__ unsigned long long g_ws_stamp[2048][4][8];
 
 namespace fgr {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWsKS = 8;                 // k32 steps (K = 256)
 constexpr int kWsPanelU = kWsKS * 128;   // 16-B units per W panel of the image
@@ -64,41 +61,14 @@ struct WsArgs {
     char* kv_img; int2* kv_sc; int n_head, kv_col0;
 };
 
-__device__ __forceinline__ float xg_sum_w(float v) {      // sum over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-__device__ __forceinline__ float xg_max_w(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-// s_waitcnt vmcnt(N) only (lgkmcnt / expcnt untouched)
-template <int N>
-__device__ __forceinline__ void wait_vm_ws() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
 // vmcnt(8 n) for a (compile-time after unrolling) n in [0, 7]
 __device__ __forceinline__ void wait_groups_ws(int n) {
     switch (n) {
-        case 0: wait_vm_ws<0>(); break;   case 1: wait_vm_ws<8>(); break;
-        case 2: wait_vm_ws<16>(); break;  case 3: wait_vm_ws<24>(); break;
-        case 4: wait_vm_ws<32>(); break;  case 5: wait_vm_ws<40>(); break;
-        case 6: wait_vm_ws<48>(); break;  default: wait_vm_ws<56>(); break;
+        case 0: wait_vm<0>(); break;   case 1: wait_vm<8>(); break;
+        case 2: wait_vm<16>(); break;  case 3: wait_vm<24>(); break;
+        case 4: wait_vm<32>(); break;  case 5: wait_vm<40>(); break;
+        case 6: wait_vm<48>(); break;  default: wait_vm<56>(); break;
     }
-}
-
-template <int ACT, bool RES>
-__device__ __forceinline__ float finish_ws(float y, float b, float r) {
-    float t = y + b;
-    if constexpr (RES) t += r;
-    if constexpr (ACT == FGR_ACT_RELU) t = fmaxf(t, 0.f);
-    return t;
 }
 
 // LNM: 0 plain A, 1 LayerNorm(A), 2 LayerNorm(A) + add, 3 as 2 plus out2 = LayerNorm(A) g2 + b2
@@ -241,7 +211,7 @@ gemm_ws_kernel(WsArgs p) {
         for (int s = 0; s < kWsKS; ++s)
             sm += ((xr[s][0] + xr[s][1]) + (xr[s][2] + xr[s][3])) +
                   ((xr[s][4] + xr[s][5]) + (xr[s][6] + xr[s][7]));
-        const float mean = xg_sum_w(sm) / 256.f;
+        const float mean = xg_sum(sm) / 256.f;
         float sq = 0.f;
 #pragma unroll
         for (int s = 0; s < kWsKS; ++s)
@@ -250,7 +220,7 @@ gemm_ws_kernel(WsArgs p) {
                 const float d = xr[s][e] - mean;
                 sq += d * d;
             }
-        const float rstd = 1.0f / sqrtf(xg_sum_w(sq) / 256.f + p.eps);
+        const float rstd = 1.0f / sqrtf(xg_sum(sq) / 256.f + p.eps);
         ln_mean = mean;
         ln_rstd = rstd;
         if (kSideLds && wv < RT) {                        // out2 rows -> LDS (stored at the end)
@@ -288,8 +258,8 @@ gemm_ws_kernel(WsArgs p) {
             mx = fmaxf(mx, max3_abs(xr[s][3], xr[s][4], xr[s][5]));
             mx = fmaxf(mx, max3_abs(xr[s][6], xr[s][7], 0.f));
         }
-        mx = xg_max_w(mx);
-        const int e = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+        mx = xg_max(mx);
+        const int e = row_scale_exp(mx);
         const float sc = __builtin_ldexpf(1.f, e);
         if (wv < RT) {
 #pragma unroll
@@ -303,7 +273,7 @@ gemm_ws_kernel(WsArgs p) {
         }
     }
     // LDS writes done, no vector-memory wait (the weight groups stay in flight)
-    __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));
+    wait_lgkm0();
     __builtin_amdgcn_s_barrier();
 #ifdef FGR_WS_STAMP
     st_[1] = __builtin_amdgcn_s_memtime();
@@ -388,8 +358,8 @@ gemm_ws_kernel(WsArgs p) {
                         mx = fmaxf(mx, max3_abs(y[rt][pp][0], y[rt][pp][1], fmaxf(fabsf(y[rt][pp][2]), fabsf(y[rt][pp][3]))));
                     }
                 }
-                mx = xg_max_w(row16_max(mx));
-                const int e = mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
+                mx = xg_max(row16_max(mx));
+                const int e = row_scale_exp(mx);
                 kv_e[pass][hh] = e;
                 const float sc = __builtin_ldexpf(1.f, e);
                 // the split of two row tiles' 4 dims at once: 16 v_fma_mix (split8_f16, the
@@ -417,10 +387,10 @@ gemm_ws_kernel(WsArgs p) {
                     if constexpr (kResEarly) r4 = rres[rt][pp];
                     const f32x4 a = acc[rt][pp];
                     constexpr int A1 = (RES && !kResEarly) ? FGR_ACT_NONE : ACT;
-                    const float4 yv = make_float4(finish_ws<A1, kResEarly>(a[0] * (rs[rt] * ws.x), bv.x, r4.x),
-                                                  finish_ws<A1, kResEarly>(a[1] * (rs[rt] * ws.y), bv.y, r4.y),
-                                                  finish_ws<A1, kResEarly>(a[2] * (rs[rt] * ws.z), bv.z, r4.z),
-                                                  finish_ws<A1, kResEarly>(a[3] * (rs[rt] * ws.w), bv.w, r4.w));
+                    const float4 yv = make_float4(finish_ct<A1, kResEarly>(a[0] * (rs[rt] * ws.x), bv.x, r4.x),
+                                                  finish_ct<A1, kResEarly>(a[1] * (rs[rt] * ws.y), bv.y, r4.y),
+                                                  finish_ct<A1, kResEarly>(a[2] * (rs[rt] * ws.z), bv.z, r4.z),
+                                                  finish_ct<A1, kResEarly>(a[3] * (rs[rt] * ws.w), bv.w, r4.w));
                     fin[pass][rt][pp] = __builtin_bit_cast(u32x4, yv);
                 }
             }
@@ -475,10 +445,10 @@ gemm_ws_kernel(WsArgs p) {
                         if constexpr (RES && !kResEarly) {
                             const float4 r4 = *reinterpret_cast<const float4*>(p.R + (int64_t)rr * p.ldr + col0 + 16 * pp + 4 * g);
                             const float4 y = __builtin_bit_cast(float4, v);
-                            v = __builtin_bit_cast(u32x4, make_float4(finish_ws<ACT, true>(y.x, 0.f, r4.x),
-                                                                      finish_ws<ACT, true>(y.y, 0.f, r4.y),
-                                                                      finish_ws<ACT, true>(y.z, 0.f, r4.z),
-                                                                      finish_ws<ACT, true>(y.w, 0.f, r4.w)));
+                            v = __builtin_bit_cast(u32x4, make_float4(finish_ct<ACT, true>(y.x, 0.f, r4.x),
+                                                                      finish_ct<ACT, true>(y.y, 0.f, r4.y),
+                                                                      finish_ct<ACT, true>(y.z, 0.f, r4.z),
+                                                                      finish_ct<ACT, true>(y.w, 0.f, r4.w)));
                         }
                         *reinterpret_cast<u32x4*>(p.C + (int64_t)rr * p.ldc + col0 + 16 * pp + 4 * g) = v;
                     }

@@ -14,7 +14,7 @@
 // dominated by the wf write. Wide-channel layers (cin % 64 == 0) run one wave per
 // query with channels on lanes (VEC contiguous floats per lane -> 16-B loads/stores);
 // narrow layers (cin < 64) run one thread per (query, kernel point).
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
@@ -72,13 +72,6 @@ __device__ __forceinline__ void store_wf(float* p, const float (&v)[VEC]) {
             __builtin_nontemporal_store(wf4{v[j], v[j + 1], v[j + 2], v[j + 3]},
                                         reinterpret_cast<wf4*>(p + j));
     }
-}
-
-__device__ __forceinline__ float kp_weight(float nx, float ny, float nz, const float* kp, int k,
-                                           float inv_extent) {
-    float dx = nx - kp[3 * k], dy = ny - kp[3 * k + 1], dz = nz - kp[3 * k + 2];
-    float d2 = dx * dx + dy * dy + dz * dz;
-    return fmaxf(1.0f - sqrtf(d2) * inv_extent, 0.0f);
 }
 
 // One wave per query, cin = 64 * VEC, K kernel points (runtime, <= kMaxKp, unrolled by KU).

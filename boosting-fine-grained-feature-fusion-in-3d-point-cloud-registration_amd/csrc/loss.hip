@@ -9,7 +9,7 @@
 //   CorrCriterion (mae)   losses/corr_loss.py:18-38         fgr_corr_loss
 //   se3_compare           utils/se3_torch.py:117-129        fgr_se3_compare
 // All reductions are deterministic (fixed lane / wave / block order).
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {

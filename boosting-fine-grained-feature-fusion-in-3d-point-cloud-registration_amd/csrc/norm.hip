@@ -1,6 +1,6 @@
 // Normalisation / embedding kernels on gfx950: segmented instance norm (per cloud),
 // row LayerNorm (+ positional add), sine coordinate embedding.
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
@@ -286,8 +286,6 @@ struct LsArgs {
     float* stats;                          // [n_seg][2][c] (mean, rstd)
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 __global__ void __launch_bounds__(256) instnorm_ls_stats_kernel(LsArgs a) {
     __shared__ float4 red[2][256];
     const int seg = blockIdx.y, chunk = blockIdx.x;
@@ -432,14 +430,8 @@ inline int ls_rows(int c) { return (256 / (c / 4)) * kLsIter; }
 template <int LPR>
 __device__ __forceinline__ float lpr_sum(float v) {
     v = row16_sum(v);
-    if constexpr (LPR >= 32) {
-        auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    }
-    if constexpr (LPR >= 64) {
-        auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    }
+    if constexpr (LPR >= 32) v = x16_sum(v);
+    if constexpr (LPR >= 64) v = x32_sum(v);
     return v;
 }
 

@@ -36,13 +36,11 @@
 // [term][g][16] x 16 B in natural k order, k32 steps padded to an even count -- layer 1's K = 32
 // image carries one zero step that is skipped -- then the per-row inverse scales). Layer 0's
 // weight and all biases are raw fp32.
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPmRing = 4;                       // register ring of load groups (3 in flight)
 
@@ -65,18 +63,6 @@ __host__ __device__ constexpr int pm_base(int l, int d) {
     int b = 0;
     for (int i = 0; i < l; ++i) b += pm_groups(i, d);
     return b;
-}
-
-__device__ __forceinline__ float xg_max_pm(float v) {     // max over lanes c, c^16, c^32, c^48
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
-// exponent e of the row scale 2^e: max 2^e in [2^14, 2^15) (0 for an all-zero row)
-__device__ __forceinline__ int pm_scale_exp(float mx) {
-    return mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
 }
 
 template <int D, int RT>
@@ -124,7 +110,7 @@ __global__ void __launch_bounds__(256, 1) pos_mlp_kernel(PosMlpArgs p) {
             h[e] = fmaxf(v, 0.f);
             mx = fmaxf(mx, h[e]);
         }
-        const int ea = pm_scale_exp(xg_max_pm(mx));
+        const int ea = row_scale_exp(xg_max(mx));
         u32x4 hi, lo;
         split8_f16(h, __builtin_ldexpf(1.f, ea), hi, lo);
         act[((wv * 8 + 0) * 2 + 0) * 64 + lane] = hi;
@@ -207,7 +193,7 @@ __global__ void __launch_bounds__(256, 1) pos_mlp_kernel(PosMlpArgs p) {
                 for (int q = 0; q < PW; ++q)
                     mx = fmaxf(mx, fmaxf(fmaxf(hid[rt][q & 3][0], hid[rt][q & 3][1]),
                                          fmaxf(hid[rt][q & 3][2], hid[rt][q & 3][3])));
-                mx = xg_max_pm(mx);
+                mx = xg_max(mx);
                 if (g == 0) wmax[wv][16 * rt + c] = mx;
             }
             __syncthreads();            // maxima visible; every wave is done reading the image
@@ -215,7 +201,7 @@ __global__ void __launch_bounds__(256, 1) pos_mlp_kernel(PosMlpArgs p) {
             for (int rt = 0; rt < RT; ++rt) {
                 const int rc = 16 * rt + c;
                 const float mx = fmaxf(fmaxf(wmax[0][rc], wmax[1][rc]), fmaxf(wmax[2][rc], wmax[3][rc]));
-                const int ea = pm_scale_exp(mx);
+                const int ea = row_scale_exp(mx);
                 inv_sc[rt] = __builtin_ldexpf(1.f, -ea);
                 const float sc = __builtin_ldexpf(1.f, ea);
 #pragma unroll

@@ -11,7 +11,7 @@
 // Two fp32-accurate variants: fgr_res2net_chain6 (three exact bf16 terms, six products;
 // w = 112, 224 -- dispatched at w = 224, where it measured faster) and fgr_res2net_chain_h3
 // (scaled split fp16, three products; w % 4 == 0 up to 224).
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
@@ -57,9 +57,6 @@ __device__ __forceinline__ void copy_rows(float* __restrict__ dst, int64_t ldd,
     }
 }
 
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int kRows = 32;
 
 // ------------------------------------------------------------------------------------
@@ -73,8 +70,6 @@ constexpr int kRows = 32;
 // wave-load), streamed two k-steps ahead. K is padded to a multiple of 32 (w = 112 -> 128)
 // with zero weights and zero A columns. 2 barriers per step (build | MFMA + epilogue).
 // ------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
     h = (__bf16)x;
@@ -209,7 +204,6 @@ res2net_chain6_kernel(const float* __restrict__ h, int64_t n, int scale, int num
 // (h, m) images img[t][ks][g][row]; W_i rows come pre-scaled per output column with their
 // inverse scales wsc[i][col] (fgreg.ops.res2net_fragments_h3).
 // ------------------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // R rows per block (32, or 48 at w = 224 when that saves a round of blocks, as in chain6).
 // Each step issues the whole step's W_i fragments (KS x 2 per lane) before the build, so the
@@ -289,7 +283,7 @@ res2net_chain_h3_kernel(const float* __restrict__ h, int64_t n, int w, int scale
             if (u >= NU) break;
             const int row = u % R, kg = u / R;
             const float mx = __int_as_float(rm[row]);
-            const float s = __builtin_ldexpf(1.f, mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0);
+            const float s = __builtin_ldexpf(1.f, row_scale_exp(mx));
             f16x8 th, tm;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -328,7 +322,8 @@ res2net_chain_h3_kernel(const float* __restrict__ h, int64_t n, int w, int scale
         for (int rg = 0; rg < RF; ++rg) {
             const int row = rg * 16 + c;
             const float mx = __int_as_float(rm[row]);
-            const float rs = __builtin_ldexpf(1.f, mx > 0.f ? -min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0);
+            // (the outer test repeats row_scale_exp's own: the negation stays inside the select)
+            const float rs = __builtin_ldexpf(1.f, mx > 0.f ? -row_scale_exp(mx) : 0);
             const f32x4 av = acc[rg];
             float4 y;
             y.x = fmaxf(av[0] * rs * wsv.x + bc.x, 0.f);

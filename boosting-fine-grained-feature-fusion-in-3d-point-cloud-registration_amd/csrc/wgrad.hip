@@ -25,14 +25,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace fgr {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kWgT = 128;                  // output tile edge
 constexpr int kWgK = 32;                   // rows per k-step
@@ -54,10 +50,6 @@ struct WgradArgs {
     float* db;         // optional: db[i] = sum_r dy[r][i] (the bias gradient)
     double* part_db;   // several chunks: its partials [chunk][m]
 };
-
-__device__ __forceinline__ int wg_scale_exp(float mx) {
-    return mx > 0.f ? min(15 - __builtin_amdgcn_frexp_expf(mx), 127) : 0;
-}
 
 // one register set of k-step rows (the next k-step's loads in flight during the matrix-core
 // work; 166 VGPRs = 3 workgroups per CU -- a second set spilled or cost the occupancy)
@@ -117,7 +109,7 @@ __global__ void __launch_bounds__(256, 3) wgrad_f16x3_kernel(WgradArgs p) {
             for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[e][q]));
             m = fmaxf(m, __shfl_xor(m, 16, 64));
             m = fmaxf(m, __shfl_xor(m, 32, 64));
-            const int en = m > 0.f ? min(ecur[q], wg_scale_exp(m)) : ecur[q];
+            const int en = m > 0.f ? min(ecur[q], row_scale_exp(m)) : ecur[q];
             if (kg == 0) edel[op][4 * c4 + q] = en - ecur[q];
             if (en != ecur[q]) chg[par] = 1;
             ecur[q] = en;

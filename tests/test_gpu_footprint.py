@@ -107,7 +107,7 @@ def _image(arena, w, split='fgr_split_weights_h3', colmajor=False):
 def _gemm(arena, m, n, k, act, res, mode='f16x3', unaligned=False, ws=None, colmajor=False):
     """One fgr_gemm_<mode>[_ws] call. unaligned: the output starts 4 bytes past a 16-B boundary
     with a row stride that is no multiple of 4 (the scalar-store epilogue, vo == 0,
-    gemm16.hip:1158). ws: None (no-workspace entry point) or a byte count relative to
+    gemm_f16x3_impl). ws: None (no-workspace entry point) or a byte count relative to
     fgr_gemm_workspace's answer (0 = exactly that, -16 = 16 fewer over the same buffer)."""
     x, w, b, r = _gemm_data(m, n, k)
     a = arena.put(x, ld=k + 4, name='a')
@@ -141,9 +141,9 @@ TILES = list('befghijklmtuvwxyz') + list('ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789')
 @pytest.mark.parametrize('tile', TILES)
 def test_gemm_f16x3_tiles_footprint(gpu, tile, monkeypatch):
     """Every f16x3 tile / pipeline variant (FGR_GEMM16_TILE, read per call by h3_tile,
-    gemm16.hip:1073) on ragged shapes: (65, 20, 40) two row tiles and a partial column tile,
+    gemm16.hip) on ragged shapes: (65, 20, 40) two row tiles and a partial column tile,
     (77, 50, 36) K % 8 != 0 -- where every g5 letter runs the k-looped dispatcher's own choice
-    (gemm16.hip:1076) -- and (130, 33, 72) odd N; bias, residual with ldr = n + 8, plain and
+    (h3_tile_kloop) -- and (130, 33, 72) odd N; bias, residual with ldr = n + 8, plain and
     ReLU-residual-LeakyReLU epilogues; once with 16-B aligned float4 stores and once through
     the scalar-store epilogue."""
     monkeypatch.setenv('FGR_GEMM16_TILE', tile)
@@ -159,10 +159,10 @@ def test_gemm_f16x3_tiles_footprint(gpu, tile, monkeypatch):
                                    (4097, 1024, 256), (8001, 224, 128), (8001, 640, 256)])
 def test_gemm_f16x3_default_dispatch_footprint(gpu, m, n, k, monkeypatch):
     """The default dispatch one ragged row past its thresholds: K = 256 with >= 4096 rows and
-    N in {256, 512, 768, 1024} is the weight-split kernel (gemm_ws_supported, gemm_ws.hip:557,
-    taken only with FGR_GEMM16_TILE unset, gemm16.hip:1173; it has the plain / ReLU epilogues
-    and the residual add, gemm_ws.hip:576); >= 8000 rows with K <= 128 and N >= 224, or
-    N >= 640, is the row-stationary 'z' (h3_tile, gemm16.hip:1084)."""
+    N in {256, 512, 768, 1024} is the weight-split kernel (gemm_ws_supported,
+    taken only with FGR_GEMM16_TILE unset, gemm_f16x3_impl; it has the plain / ReLU epilogues
+    and the residual add, gemm_ws_f16x3); >= 8000 rows with K <= 128 and N >= 224, or
+    N >= 640, is the row-stationary 'z' (h3_tile)."""
     monkeypatch.delenv('FGR_GEMM16_TILE', raising=False)
     for act, res in [(ACT_NONE, True), (ACT_RELU, False)] + ([(ACT_RELU_RES_LEAKY, True)] if m == 8001 else []):
         out = _both(lambda ar: _gemm(ar, m, n, k, act, res), gpu)
@@ -172,9 +172,9 @@ def test_gemm_f16x3_default_dispatch_footprint(gpu, m, n, k, monkeypatch):
 
 @pytest.mark.parametrize('mode', ['f16x3', 'bf16'])
 def test_gemm_splitk_exact_workspace(gpu, mode, monkeypatch):
-    """Split-K (2120 x 128 x 1920, splitk_shape via h3_tile_kloop, gemm16.hip:1096) with exactly
+    """Split-K (2120 x 128 x 1920, splitk_shape via h3_tile_kloop) with exactly
     fgr_gemm_workspace's bytes, 0xFF-prefilled in the poisoned run; and with ws_bytes 16
-    smaller, which the header says runs unsplit (gemm16.hip:1191) -- same contract, so the same
+    smaller, which the header says runs unsplit (gemm_f16x3_impl) -- same contract, so the same
     bound, and the workspace then stays untouched."""
     monkeypatch.delenv('FGR_GEMM16_TILE', raising=False)
     monkeypatch.delenv('FGR_GEMM_BF16_TILE', raising=False)
@@ -219,8 +219,8 @@ def test_gemm_bf16_tiles_footprint(gpu, tile, monkeypatch):
 def test_weight_image_exact_bytes(gpu, split, n, k, colmajor, monkeypatch):
     """Weight images in exact-*_bytes scratch views: (3, 36) and (17, 8) partial 16-row panels and
     K-padding, (200, 1000) the largest of the fused split's range (k <= kSplitFusedK = 1024,
-    gemm16.hip:1014), (33, 1032) past it the scale pass + split pass, and with stride_n == 1 the
-    column-major scale pass (gemm16.hip:1020). The GEMM
+    fgr_split_weights_h3), (33, 1032) past it the scale pass + split pass, and with stride_n == 1 the
+    column-major scale pass (its k >= 1024 branch). The GEMM
     consuming the image built over 0x00 and over 0xFF bytes must give bit-identical output
     (the arena checks nothing was written past the reported bytes); the image bytes themselves
     are compared too and a difference is reported as don't-care bytes."""
@@ -320,7 +320,7 @@ def test_ffn_footprint(gpu, m, f, in_place):
 
 @pytest.mark.parametrize('m,d', [(97, 64), (333, 128)])
 def test_corr_head_footprint(gpu, m, d):
-    """fgr_corr_head_f16x3 (two row-stationary launches, gemm16.hip:1314): hidden (m, d) is
+    """fgr_corr_head_f16x3 (two row-stationary launches, gemm16.hip): hidden (m, d) is
     caller scratch of exactly 4 m d bytes, corr (m, 3) and logits (m) contiguous guarded
     outputs, f strided. Bound of test_corr_head_fused_vs_fp64: 1e-5 of each row's
     |.|-weighted magnitude."""
@@ -406,7 +406,7 @@ def _attn_split(ar, name, nhead, d, short=0):
 
 @pytest.mark.parametrize('d', [256, 512])
 def test_attention_f16x3_footprint(gpu, d):
-    """fgr_attention_f16x3 (attention16.hip:1065, head dim 32 / 64) on the segment sets of
+    """fgr_attention_f16x3 (attention_f16x3_impl, head dim 32 / 64) on the segment sets of
     test_attention_split_is_fp32_accurate (partial and 1-key tiles, key segments != query
     segments), ld = d + 4, the workspace exactly fgr_attention_f16x3_workspace bytes: 1e-5 vs
     fp64."""
@@ -420,7 +420,7 @@ def test_attention_f16x3_footprint(gpu, d):
 
 @pytest.mark.parametrize('d', [256, 512])
 def test_attention_bf16_footprint(gpu, d):
-    """fgr_attention_bf16 (bf16.hip:636), same cases; test_attention_bf16's bound vs exact fp64
+    """fgr_attention_bf16 (bf16.hip), same cases; test_attention_bf16's bound vs exact fp64
     at O(1) scores: 1e-2."""
     def run(ar):
         rc, o, _ = _attn_split(ar, 'fgr_attention_bf16', 8, d)
@@ -433,7 +433,7 @@ def test_attention_bf16_footprint(gpu, d):
 @pytest.mark.parametrize('name', ['fgr_attention_f16x3', 'fgr_attention_bf16'])
 def test_attention_refuses_short_workspace(gpu, name):
     """ws_bytes 16 below the kernel's own need (head dim 64, where fgr_*_workspace reports
-    exactly that) is refused before the first launch (attention16.hip:1090, bf16.hip:659):
+    exactly that) is refused before the first launch (attention_f16x3_impl, fgr_attention_bf16):
     non-zero status, a message, output and workspace untouched."""
     ar = Arena(gpu, poison=True)
     rc, o, ws = _attn_split(ar, name, 8, 512, short=16)
@@ -486,8 +486,8 @@ def _instnorm_call(ar, x, div, res, lens, short=0):
 @pytest.mark.parametrize('lens,c', [([700, 1, 33, 512], 72), ([1025, 2], 64)])
 def test_instnorm_footprint(gpu, lens, c):
     """fgr_instnorm with row_div and residual: [700, 1, 33, 512] x 72 is the one-launch register
-    path (segments <= kSegRows = 1024, norm.hip:684; no workspace), [1025, 2] x 64 one row past
-    it the three-launch long-segment path (ls_ok, norm.hip:695) over exactly
+    path (segments <= kSegRows = 1024, fgr_instnorm; no workspace), [1025, 2] x 64 one row past
+    it the three-launch long-segment path (ls_ok) over exactly
     fgr_instnorm_workspace bytes."""
     rng = np.random.default_rng(5)
     n = sum(lens)
@@ -507,7 +507,7 @@ def test_instnorm_footprint(gpu, lens, c):
 
 
 def test_instnorm_refuses_short_workspace(gpu):
-    """The long-segment path checks ws_bytes before its first launch (norm.hip:699)."""
+    """The long-segment path checks ws_bytes before its first launch (fgr_instnorm)."""
     lens, c = [1025, 2], 64
     n = sum(lens)
     ar = Arena(gpu, poison=True)
@@ -525,7 +525,7 @@ def test_instnorm_refuses_short_workspace(gpu):
 def test_layernorm_footprint(gpu, d):
     """fgr_layernorm with add and pre_bias (x is a documented in/out: x += pre_bias) at 67 rows:
     d = 32 layernorm_kernel<1>, 96 layernorm_kernel<4>, 256 the vector path
-    layernorm_lpr_kernel<32, 2> (norm.hip:739-770); 67 rows leave the last 8- / 4-row block
+    layernorm_lpr_kernel<32, 2> (fgr_layernorm); 67 rows leave the last 8- / 4-row block
     partial. fgr_layernorm_dual on the same rows."""
     n = 67
     g = torch.Generator().manual_seed(d)
@@ -613,10 +613,10 @@ def _table(rng, nq, ns, H):
 @pytest.mark.parametrize('cin', [1, 16, 32, 64, 128])
 def test_kpconv_gather_footprint(gpu, cin, H):
     """fgr_kpconv_gather at 300 queries over 257 supports: cin 1 the stem kernel, 16 / 32 the
-    quad-lane kernels, 64 / 128 the wide kernels (kpconv.hip:492-520); H = 7 and 50. A quarter of
+    quad-lane kernels, 64 / 128 the wide kernels (fgr_kpconv_gather); H = 7 and 50. A quarter of
     the table is the shadow index ns; the supports and features end exactly at row ns, so s[ns]
     and x[ns] are NaN in the poisoned run: "the shadow row is never read" is the bit-equality.
-    fgr_kpconv_gather_workspace reports 0 bytes (kpconv.hip:474), so no workspace is passed."""
+    fgr_kpconv_gather_workspace reports 0 bytes (kpconv.hip), so no workspace is passed."""
     nq, ns, n_kp, ext = 300, 257, 15, 0.5
     rng = np.random.default_rng(cin + H)
     s = rng.uniform(-1, 1, (ns, 3)).astype(np.float32)
@@ -647,7 +647,7 @@ def test_kpconv_gather_footprint(gpu, cin, H):
 
 @pytest.mark.parametrize('c', [33, 64])
 def test_max_pool_footprint(gpu, c):
-    """fgr_max_pool: c = 33 the per-element kernel, 64 the wave-per-row kernel (kpconv.hip:536);
+    """fgr_max_pool: c = 33 the per-element kernel, 64 the wave-per-row kernel (kpconv.hip);
     shadow entries read as 0, never x[ns]."""
     nq, ns, H = 300, 257, 9
     rng = np.random.default_rng(c)
@@ -687,8 +687,8 @@ def _ln_data(m, n, k):
 @pytest.mark.parametrize('side', [False, True])
 def test_gemm_ln_footprint(gpu, m, n, k, side, monkeypatch):
     """fgr_gemm_f16x3_ln / _ln_out2 one ragged row past the smallest supported row counts:
-    4097 x 768 x 256 the weight-split kernel with the LN prologue (gemm_ws_ln_supported,
-    gemm_ws.hip:567), 8001 x 640 x 256 the row-stationary one (h3_tile 'z', gemm16.hip:1084);
+    4097 x 768 x 256 the weight-split kernel with the LN prologue (gemm_ws_ln_supported),
+    8001 x 640 x 256 the row-stationary one (h3_tile 'z');
     x, add, c and out2 strided by + 4. 1e-5 vs fp64 (test_gemm_ln_vs_fp64), the side output
     1e-6 (test_ln_qkv_images_vs_two_launch_path)."""
     monkeypatch.delenv('FGR_GEMM16_TILE', raising=False)
@@ -739,7 +739,7 @@ def _attend_img(ar, fn, q, ld_q, img, lens, kv, n, d, nh):
 
 def test_gemm_ln_qkv_footprint(gpu, monkeypatch):
     """fgr_gemm_f16x3_ln_qkv at 4097 rows (d 256, 8 heads of 32: the weight-split kernel's K / V
-    image epilogue, gemm_ws.hip:603) into an exact-fgr_kv_image_bytes scratch view, with the
+    image epilogue, gemm_ws_f16x3) into an exact-fgr_kv_image_bytes scratch view, with the
     side output; the images are checked by feeding them to fgr_attention_f16x3_img: its output
     is bit-equal between the clean and the 0xFF-prefilled run and within 1e-5 of fp64. Segments
     start inside 64-row tiles (incl. a 1-row cloud); the last tile holds 1 row."""
@@ -768,7 +768,7 @@ def test_gemm_ln_qkv_footprint(gpu, monkeypatch):
 @pytest.mark.parametrize('mode', ['f16x3', 'bf16'])
 def test_gemm_qkv_dh64_footprint(gpu, mode, monkeypatch):
     """fgr_gemm_f16x3_qkv / fgr_gemm_bf16_qkv (head dim 64: the staged 64 x 128 g5 epilogue,
-    gemm16.hip:1366 / bf16.hip:700) at m = 130, d = 128, 2 heads: three row tiles, the last with
+    gemm16.hip / bf16.hip) at m = 130, d = 128, 2 heads: three row tiles, the last with
     2 rows, segments [65, 1, 64] crossing tiles; K / V images in exact fgr_kv_image[_bf16]_bytes
     views, consumed by fgr_attention_f16x3_img / _bf16_img. 1e-5 vs fp64 (f16x3,
     test_qkv_images_dh64_vs_two_launch_path), 1e-2 (bf16, test_bf16_qkv_images_vs_two_launch_path)."""
@@ -821,9 +821,9 @@ def test_gemm_qkv_dh64_footprint(gpu, mode, monkeypatch):
 @pytest.mark.parametrize('kind,w', [('h3', 28), ('h3', 56), ('h3', 112), ('h3', 224), ('x6', 112),
                                     ('x6', 224)])
 def test_res2net_chain_footprint(gpu, kind, w, n):
-    """fgr_res2net_chain_h3 (16-column tile counts 2 / 4 / 7 / 14, res2net.hip:391; width 28 pads
+    """fgr_res2net_chain_h3 (16-column tile counts 2 / 4 / 7 / 14, res2net.hip; width 28 pads
     its last tile) and fgr_res2net_chain6 (112, 224; 16-row blocks below 32 rows at 224,
-    res2net.hip:421) at 1 row, 65 (a 1-row last block) and 150 rows; scale 8, cin 32, the
+    FGR_R2N_ROWS) at 1 row, 65 (a 1-row last block) and 150 rows; scale 8, cin 32, the
     fragment images and scales in exact-size views, ld_cat = scale w + cin + 4: nothing past
     column scale w + cin of cat is written. TOL vs fp64 (test_res2net_block_vs_oracle)."""
     from fgreg import ops
@@ -953,8 +953,8 @@ def test_radius_search_footprint(gpu, mode):
 @pytest.mark.parametrize('which', ['count', 'fill', 'build', 'search'])
 def test_geometry_refuses_short_workspace(gpu, which):
     """ws_bytes / grid_bytes 16 below the reported size is refused before the first launch
-    (grid.hip:681, :719, :747, :787): non-zero status, a message, outputs and workspace
-    untouched."""
+    (fgr_grid_subsample_count / _fill, fgr_radius_grid_build, fgr_radius_search_grid):
+    non-zero status, a message, outputs and workspace untouched."""
     P, lens = _clouds()
     n, nc = len(P), len(lens)
     ar = Arena(gpu, poison=True)

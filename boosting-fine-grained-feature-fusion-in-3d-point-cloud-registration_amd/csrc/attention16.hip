@@ -938,9 +938,8 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
 }  // namespace
 
 // fgr_attention_bwd_train on the f16 matrix cores (called from train.hip): the K / V / Q / dO
-// per-tile images, then attn_bwd_dq_f16x3_kernel and (dkdv) attn_bwd_dkdv_f16x3_kernel; without
-// dkdv, lse_out / dsum_out receive the rows' lse2 and D for train.hip's fp32-MFMA dK / dV
-// kernel. q_off and kv_off index one packed row space of n_rows rows (q and kv segments of the
+// per-tile images, then attn_bwd_dq_f16x3_kernel and attn_bwd_dkdv_f16x3_kernel.
+// q_off and kv_off index one packed row space of n_rows rows (q and kv segments of the
 // same tensors, self- or cross-attention). ws: attn_bwd_f16x3_bytes.
 size_t attn_bwd_f16x3_bytes(int64_t n_rows, int32_t n_seg, int32_t n_head, int32_t dh) {
     const int64_t nt = n_tiles16(n_rows, n_seg) * n_head;
@@ -954,7 +953,7 @@ int attn_bwd_f16x3(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                    const int64_t* q_off, const int64_t* kv_off, const int32_t* kv_seg,
                    int32_t n_seg, int32_t n_kv_seg, int64_t n_rows, int64_t max_q_len,
                    int64_t max_kv_len, int32_t nhead, int32_t dh, float scale, const float* lse_in,
-                   float* lse_out, float* dsum_out, bool dkdv, void* ws, uint32_t drop_seed,
+                   float* dsum_out, void* ws, uint32_t drop_seed,
                    uint32_t drop_thresh, float inv_keep, hipStream_t st) {
     const int32_t nsm = std::max(n_seg, n_kv_seg);
     const int64_t nt = n_tiles16(n_rows, nsm) * nhead;
@@ -973,33 +972,31 @@ int attn_bwd_f16x3(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                  {img(0), img(1), img(2), img(3)}, {sc(0), sc(1), sc(2), sc(3)},
                  {n_kv_seg, n_kv_seg, n_seg, n_seg}, {1, 0, 1, 1}, nsm};
     const dim3 igrid((unsigned)ceil_div(std::max(max_q_len, max_kv_len), 64), (unsigned)nhead,
-                     (unsigned)((dkdv ? 4 : 2) * nsm));
+                     (unsigned)(4 * nsm));
 #define FGR_BWD16(D)                                                                                 \
     hipLaunchKernelGGL(attn_image16_jobs_kernel<D>, igrid, dim3(256), 0, st, jobs);                   \
     if (drop)                                                                                        \
         hipLaunchKernelGGL((attn_bwd_dq_f16x3_kernel<D, true>), dim3((unsigned)n_blocks), dim3(256), 0, st, \
                            q, ldq, dout, lddo, o, ldo, img(0), sc(0), img(1), sc(1), dq, lddq, q_off,   \
                            kv_off, kv_seg, nhead, n_seg, n_qblk, scale, sl2, lse_in,                  \
-                           dkdv ? nullptr : lse_out, dsum_out, dkdv ? lsed : nullptr, drop_seed,      \
+                           nullptr, dsum_out, lsed, drop_seed,                                        \
                            drop_thresh, inv_keep);                                                   \
     else                                                                                             \
         hipLaunchKernelGGL((attn_bwd_dq_f16x3_kernel<D, false>), dim3((unsigned)n_blocks), dim3(256), 0, st, \
                            q, ldq, dout, lddo, o, ldo, img(0), sc(0), img(1), sc(1), dq, lddq, q_off,   \
                            kv_off, kv_seg, nhead, n_seg, n_qblk, scale, sl2, lse_in,                  \
-                           dkdv ? nullptr : lse_out, dsum_out, dkdv ? lsed : nullptr, drop_seed,      \
+                           nullptr, dsum_out, lsed, drop_seed,                                        \
                            drop_thresh, inv_keep);                                                   \
-    if (dkdv) {                                                                                      \
-        if (drop)                                                                                    \
-            hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, true>), dim3((unsigned)n_kblocks), dim3(256), 0, \
-                               st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv,  \
-                               lddv, q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale,   \
-                               sl2, drop_seed, drop_thresh, inv_keep);                               \
-        else                                                                                         \
-            hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, false>), dim3((unsigned)n_kblocks), dim3(256), 0, \
-                               st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv,  \
-                               lddv, q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale,   \
-                               sl2, drop_seed, drop_thresh, inv_keep);                               \
-    }
+    if (drop)                                                                                        \
+        hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, true>), dim3((unsigned)n_kblocks), dim3(256), 0, \
+                           st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv,      \
+                           lddv, q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale,       \
+                           sl2, drop_seed, drop_thresh, inv_keep);                                   \
+    else                                                                                             \
+        hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, false>), dim3((unsigned)n_kblocks), dim3(256), 0, \
+                           st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv,      \
+                           lddv, q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale,       \
+                           sl2, drop_seed, drop_thresh, inv_keep);
     if (dh == 32) {
         FGR_BWD16(32)
     } else {

@@ -449,47 +449,28 @@ static int attention_bwd_impl(const float* q, int64_t ldq, const float* k, int64
     const bool drop = drop_p > 0.f;
     hipStream_t st = as_stream(stream);
     dim3 g1((unsigned)(n_seg * a.q_blocks), nhead), g2((unsigned)(n_kv_seg * a.kv_blocks), nhead);
-    // head dim 16 / 32 / 64 with 16-B aligned rows: the fp32-MFMA kernels (FGR_ATTN_BWD=scalar:
-    // the scalar ones, for A/B)
+    // head dim 16 / 32 / 64 with 16-B aligned rows: the fp32-MFMA kernels
     const bool al = ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
                       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o) |
                       reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dq) |
                       reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) & 15) == 0 &&
                     (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) % 4 == 0;
-    static const bool scalar_only = [] { const char* e = getenv("FGR_ATTN_BWD"); return e && e[0] == 's'; }();
-    const bool mfma = al && !scalar_only && (dh == 16 || dh == 32 || dh == 64);
+    const bool mfma = al && (dh == 16 || dh == 32 || dh == 64);
     FGR_REQUIRE(!drop || (al && (dh == 16 || dh == 32 || dh == 64)),
                 "fgr_attention_bwd_drop: dropout needs head dim 16 / 32 / 64 and 16-B aligned rows");
     // training with the forward's lse (head dim 32 / 64): the f16x3 kernels (attention16.hip
     // attn_bwd_f16x3), their K / V / Q / dO images after lse / D in ws
-    // (fgr_attention_bwd_train_workspace). FGR_ATTN_BWD16=0: the fp32-MFMA kernels, =q: only dQ
-    // on the f16 matrix cores (A/B)
-    static const int bwd16 = [] {
-        const char* e = getenv("FGR_ATTN_BWD16");
-        return e && e[0] == '0' ? 0 : e && e[0] == 'q' ? 1 : 2;
-    }();
+    // (fgr_attention_bwd_train_workspace)
     const size_t lse_bytes = (need + 255) & ~(size_t)255;
     const int64_t n_rows = std::max(nq, n_kv_rows);
-    if (bwd16 && lse_in && n_kv_rows >= 0 && al && (dh == 32 || dh == 64) &&
+    if (lse_in && n_kv_rows >= 0 && al && (dh == 32 || dh == 64) &&
         ws_bytes >= lse_bytes + attn_bwd_f16x3_bytes(n_rows, std::max(n_seg, n_kv_seg), nhead, dh)) {
         FGR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "fgr_attention_bwd_train: ws alignment");
-        const bool dkdv16 = bwd16 == 2;
-        const int rc = attn_bwd_f16x3(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dq, lddq, dk, lddk, dv,
-                                      lddv, q_off, kv_off, kv_seg, n_seg, n_kv_seg, n_rows, max_q_len,
-                                      max_kv_len, nhead, dh, scale, lse_in, a.lse, a.dsum, dkdv16,
-                                      static_cast<char*>(ws) + lse_bytes, a.drop_seed,
-                                      a.drop_thresh, a.inv_keep, st);
-        if (rc != FGR_OK || dkdv16) return rc;
-        switch (dh) {
-#define AT16(D) case D: \
-            if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_mfma_kernel<D, true>), g2, dim3(256), 0, st, a); \
-            else hipLaunchKernelGGL((attn_bwd_dkdv_mfma_kernel<D, false>), g2, dim3(256), 0, st, a); \
-            break;
-            AT16(32) AT16(64)
-#undef AT16
-        }
-        FGR_CHECK_LAUNCH("attn_bwd_dkdv_mfma_kernel");
-        return FGR_OK;
+        return attn_bwd_f16x3(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dq, lddq, dk, lddk, dv,
+                              lddv, q_off, kv_off, kv_seg, n_seg, n_kv_seg, n_rows, max_q_len,
+                              max_kv_len, nhead, dh, scale, lse_in, a.dsum,
+                              static_cast<char*>(ws) + lse_bytes, a.drop_seed, a.drop_thresh,
+                              a.inv_keep, st);
     }
     if (drop) {
         switch (dh) {

@@ -496,11 +496,8 @@ char bf16_tile(int m, int n, int k) {
 int bf16_ksplit(char cfg, int m, int n, int k) {
     int bm, bn;
     if (k % 8 != 0 || !g5_tile(cfg, &bm, &bn)) return 1;
-    const char* on = getenv("FGR_GEMM_SPLITK");
     const char* f = getenv("FGR_GEMM_KSPLIT");
     if (f && f[0]) return g5_ksplit(m, n, k, bm, bn);
-    if (on && on[0] == '0') return 1;
-    if (on && on[0] == '1') return g5_ksplit(m, n, k, bm, bn);
     return splitk_shape(m, n, k) ? (k >= 2048 ? 4 : 2) : 1;
 }
 }  // namespace fgr

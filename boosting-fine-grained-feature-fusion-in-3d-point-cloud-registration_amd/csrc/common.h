@@ -228,7 +228,7 @@ int attn_bwd_f16x3(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                    const int64_t* q_off, const int64_t* kv_off, const int32_t* kv_seg,
                    int32_t n_seg, int32_t n_kv_seg, int64_t n_rows, int64_t max_q_len,
                    int64_t max_kv_len, int32_t nhead, int32_t dh, float scale, const float* lse_in,
-                   float* lse_out, float* dsum_out, bool dkdv, void* ws, uint32_t drop_seed,
+                   float* dsum_out, void* ws, uint32_t drop_seed,
                    uint32_t drop_thresh, float inv_keep, hipStream_t st);
 
 // gemm_ws.hip: the weight-split row-stationary f16x3 GEMM (K = 256, N = 256 / 768, many rows);

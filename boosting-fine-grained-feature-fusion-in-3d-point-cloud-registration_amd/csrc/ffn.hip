@@ -51,16 +51,6 @@
 
 #include "mfma.h"
 
-#ifdef FGR_FFN_STAMP
-// Diagnostic build only (tools/ffn_stamp.py): per (block, wave) cycle sums of the loop's phases
-// (s_memtime): [0] prologue, [1] waits for the DMA, [2] barriers, [3] DMA + read issue, [4] MFMA
-// sections (incl. the hidden epilogue), [5] read waits, [6] epilogue, [7] total
-__device__ unsigned long long g_ffn_stamp[4096][4][8];
-#define FFN_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define FFN_T(v)
-#endif
-
 namespace fgr {
 namespace {
 
@@ -164,10 +154,6 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
     __shared__ float4 cw2[kFfnD / 4], cb2[kFfnD / 4];           // linear2
     __shared__ float4 lng[kFfnD / 4], lnb[kFfnD / 4];           // LayerNorm3 gamma / beta
 
-#ifdef FGR_FFN_STAMP
-    unsigned long long acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    FFN_T(t_begin);
     const int nbm = (p.M + 63) / 64;
     int t = blockIdx.x;
     {   // XCD-aware order: each XCD a contiguous range of row blocks
@@ -303,10 +289,6 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
     f32x4 acc1[2];
     f16x8 hb[2];
     read_wait(wa);
-    FFN_T(t_loop);
-#ifdef FGR_FFN_STAMP
-    acc_[0] = t_loop - t_begin;
-#endif
     for (int ch2 = 0; ch2 < nch; ch2 += 2) {            // one ring turn (8 units) per iteration
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
@@ -315,25 +297,16 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
             u32x4 (&cur)[16] = (jj & 1) ? wb : wa;
             u32x4 (&nxt)[16] = (jj & 1) ? wa : wb;
             const bool more = u + 1 < nu;                 // block-uniform
-            FFN_T(t0);
             if (more) {
                 // unit u + 1 landed (units issued after it: min(6, nu - 2 - u)); every wave has
                 // read unit u (its fragments are in registers), whose slot the DMA of unit u + 8
                 // refills
                 wait_units(min(kRing - 2, nu - 2 - u));
-                FFN_T(t1);
                 __builtin_amdgcn_s_barrier();
-                FFN_T(t2);
                 if (u + kRing < nu) dma(u + kRing, jj);
                 read_issue(ring_slot(jj + 1), lane_u, nxt);
-#ifdef FGR_FFN_STAMP
-                acc_[1] += t1 - t0;
-                acc_[2] += t2 - t1;
-                acc_[3] += __builtin_amdgcn_s_memtime() - t2;
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);
-            FFN_T(t3);
             if (j < 2) {
                 f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -370,15 +343,9 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            FFN_T(t4);
             if (more) read_wait(nxt);
-#ifdef FGR_FFN_STAMP
-            acc_[4] += t4 - t3;
-            acc_[5] += __builtin_amdgcn_s_memtime() - t4;
-#endif
         }
     }
-    FFN_T(t_epi);
 
     // 6. y = acc * wsc2 / S + b2 + x: lane (g, c) holds row c, columns 16 q + 4 g .. + 3
     const bool ok = mw + c < p.M;
@@ -397,13 +364,6 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
                                      fmaf(accy[q][3], w4.w * inv_s, b4.w) + res[q].w);
         if (ok) *reinterpret_cast<float4*>(orow + n) = y;
     }
-#ifdef FGR_FFN_STAMP
-    __builtin_amdgcn_s_waitcnt(0);
-    FFN_T(t_end);
-    acc_[6] = t_end - t_epi;
-    acc_[7] = t_end - t_begin;
-    if (lane < 8 && blockIdx.x < 4096) g_ffn_stamp[blockIdx.x][wv][lane] = acc_[lane];
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -886,38 +846,24 @@ extern "C" int fgr_ffn_f16x3_act(const float* x, int64_t ldx, const float* gamma
               (const u32x4*)i1, (const float*)(i1 + (size_t)(f / 16) * kFfnKS * 128 * 16), b1,
               (const u32x4*)i2, (const float*)(i2 + ffn_image_bytes(d, f)), b2,
               bound, out, ldo, m, f};
-    // FGR_FFN_V=1: the LDS-ring version (A/B); default the weight-split version 2 (f % 128 == 0)
-    static const int ver = [] { const char* e = getenv("FGR_FFN_V"); return (e && e[0] == '1') ? 1 : 2; }();
+    // the weight-split version 2 where f % 128 == 0, else the LDS-ring version
     // row tiles per block (version 2): 3 when 48-row blocks fit one round of the CUs and
-    // 64-row ones do not fill them, else 4 (FGR_FFN_RT overrides: A/B)
-    static const int rt_env = [] { const char* e = getenv("FGR_FFN_RT"); return e ? atoi(e) : 0; }();
-    const int rt = (rt_env >= 1 && rt_env <= 4) ? rt_env
-                   : ((m + 47) / 48 <= kCusFfn && (m + 63) / 64 < kCusFfn) ? 3 : 4;
+    // 64-row ones do not fill them, else 4
+    const bool rt3 = (m + 47) / 48 <= kCusFfn && (m + 63) / 64 < kCusFfn;
     if (act == FGR_ACT_GELU) {
-        // the weight-split kernel whatever FGR_FFN_V / FGR_FFN_RT say (f % 128 == 0:
-        // _act_supported), always with 48-row blocks: the RT = 4 GELU instantiation does not
-        // fit the registers (272 B of scratch per lane; RT = 3: 216 VGPRs, none), so it is not
-        // built, and row counts past 48 x 256 take more than one round of the CUs
+        // the weight-split kernel (f % 128 == 0: _act_supported), always with 48-row blocks:
+        // the RT = 4 GELU instantiation does not fit the registers (272 B of scratch per lane;
+        // RT = 3: 216 VGPRs, none), so it is not built, and row counts past 48 x 256 take more
+        // than one round of the CUs
         const unsigned nb = (unsigned)((m + 47) / 48);
         hipLaunchKernelGGL((ffn_nsplit_kernel<3, FGR_ACT_GELU>), dim3(nb), dim3(256), 0, st, a);
-    } else if (ver == 2 && f % 128 == 0) {
-        const unsigned nb = (unsigned)((m + 16 * rt - 1) / (16 * rt));
-        switch (rt) {
-            case 1: hipLaunchKernelGGL(ffn_nsplit_kernel<1>, dim3(nb), dim3(256), 0, st, a); break;
-            case 2: hipLaunchKernelGGL(ffn_nsplit_kernel<2>, dim3(nb), dim3(256), 0, st, a); break;
-            case 3: hipLaunchKernelGGL(ffn_nsplit_kernel<3>, dim3(nb), dim3(256), 0, st, a); break;
-            default: hipLaunchKernelGGL(ffn_nsplit_kernel<4>, dim3(nb), dim3(256), 0, st, a); break;
-        }
+    } else if (f % 128 == 0) {
+        if (rt3)
+            hipLaunchKernelGGL(ffn_nsplit_kernel<3>, dim3((unsigned)((m + 47) / 48)), dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL(ffn_nsplit_kernel<4>, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, st, a);
     } else
         hipLaunchKernelGGL(ffn_f16x3_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, st, a);
     FGR_CHECK_LAUNCH("ffn_f16x3_kernel");
     return FGR_OK;
 }
-
-#ifdef FGR_FFN_STAMP
-extern "C" int fgr_debug_ffn_stamps(void* dst, int32_t nblocks) {
-    if (nblocks > 4096) nblocks = 4096;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_ffn_stamp), (size_t)nblocks * 4 * 8 * 8, 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -943,8 +943,7 @@ extern "C" int fgr_split_weights_h3(const float* w, int32_t n, int32_t k, int64_
     const int npad = (n + 15) / 16 * 16;
     float* wsc = reinterpret_cast<float*>(static_cast<char*>(img) + image_bytes_h3(n, k));
     hipStream_t st = as_stream(stream);
-    static const bool fused_on = [] { const char* e = getenv("FGR_SPLIT_FUSED"); return !(e && e[0] == '0'); }();
-    if (k <= kSplitFusedK && fused_on) {
+    if (k <= kSplitFusedK) {
         hipLaunchKernelGGL(split_weights_h3_fused_kernel, dim3((unsigned)(npad / 16)), dim3(256), 0, st,
                            w, n, k, stride_n, stride_k, ksteps, wsc, (u32x4*)img);
         FGR_CHECK_LAUNCH("split_weights_h3_fused_kernel");
@@ -1012,9 +1011,8 @@ char h3_tile(int m, int n, int k) {
     // measured faster than the k-looped choice (profiles/r03_gemm_rs_sweep3.txt: 9544 x 1792 x
     // 256 1.37x, x 1024 x 256 1.17x, x 768 x 256 1.10x, 57264 x 256 x 256 1.46x, K <= 128 with
     // N >= 224 1.0-1.41x; narrow outputs, short row counts and N = 256-512 at ~10k rows stay on
-    // the k-looped kernels). FGR_GEMM_RS=0 disables.
-    static const bool rs_on = [] { const char* e = getenv("FGR_GEMM_RS"); return !(e && e[0] == '0'); }();
-    if (rs_on && k % 8 == 0 && k <= 256 && n % 16 == 0 && m >= 8000 &&
+    // the k-looped kernels).
+    if (k % 8 == 0 && k <= 256 && n % 16 == 0 && m >= 8000 &&
         (n >= 640 || (k <= 128 && n >= 224) || (m >= 25000 && n >= 224)))
         return 'z';
     return h3_tile_kloop(m, n, k);
@@ -1029,9 +1027,8 @@ char h3_tile_kloop(int m, int n, int k) {
     if (g5ok && splitk_shape(m, n, k)) return k >= 2048 ? 'X' : 'W';
     // short row counts with a long contraction and wide outputs (3DMatch's 2120 x 1024 x 2048
     // KPConv product): the 64 x 64 staged g5 'X' -- 82.0 -> 51.4 us in the forward
-    // (profiles/r05_gemm_longk_ab.txt; 'Y' before). FGR_GEMM_LONGK=0: the old choice (A/B)
-    static const bool longk = [] { const char* e = getenv("FGR_GEMM_LONGK"); return !(e && e[0] == '0'); }();
-    if (longk && g5ok && m <= 4096 && k >= 2048 && n >= 512) return 'X';
+    // (profiles/r05_gemm_longk_ab.txt; 'Y' before).
+    if (g5ok && m <= 4096 && k >= 2048 && n >= 512) return 'X';
     // (K >= 2048 took 'S' until round 5; the training backward's 4753 x 256 x 4792 runs 1.4x
     // faster on 'W', profiles/r05_gemm_train_tiles.txt)
     if (g5ok && tiles64 <= 400 && k >= 512 && n >= 32)
@@ -1048,17 +1045,13 @@ char h3_tile_kloop(int m, int n, int k) {
     return k <= 1024 ? 't' : 'e';
 }
 
-// split-K parts for a g5 variant (1 = none): by default only the measured shapes
-// (splitk_shape; 4 parts at K >= 2048, else 2), FGR_GEMM_SPLITK=0 never, =1 the automatic
-// factor (g5_ksplit) for any g5 variant; FGR_GEMM_KSPLIT forces one
+// split-K parts for a g5 variant (1 = none): only the measured shapes (splitk_shape; 4 parts
+// at K >= 2048, else 2); FGR_GEMM_KSPLIT forces one
 int h3_ksplit(char cfg, int m, int n, int k) {
     int bm, bn;
     if (k % 8 != 0 || !g5_tile(cfg, &bm, &bn)) return 1;
-    const char* on = getenv("FGR_GEMM_SPLITK");
     const char* f = getenv("FGR_GEMM_KSPLIT");
     if (f && f[0]) return g5_ksplit(m, n, k, bm, bn);
-    if (on && on[0] == '0') return 1;
-    if (on && on[0] == '1') return g5_ksplit(m, n, k, bm, bn);
     return splitk_shape(m, n, k) ? (k >= 2048 ? 4 : 2) : 1;
 }
 }  // namespace fgr

@@ -55,14 +55,6 @@
 
 #include "mfma.h"
 
-#ifdef FGR_RS_STAMP
-// Diagnostic build only (tools/build_stamp.sh, tools/rs_stamp.py): per-block clock stamps of
-// the rs kernel, read back by fgr_debug_rs_stamps. [0] s_memrealtime at entry, [1]
-// s_memtime at entry, [2] after the prologue (rows loaded and split), [3] after panel 0's
-// barrier, [4] after the last panel's barrier, [5] at exit, [6] s_memrealtime at exit, [7]
-// panels of the block.
-__device__ unsigned long long g_rs_stamp[1 << 14][8];
-#endif
 
 namespace fgr {
 namespace {
@@ -150,11 +142,6 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
     __shared__ float4 kvbuf[KV ? 4 : 1][KV ? 16 : 1][8];
     static_assert(!KV || RT == 1, "KV images: one 64-row tile per block");
 
-#ifdef FGR_RS_STAMP
-    unsigned long long st_[8];
-    st_[0] = __builtin_amdgcn_s_memrealtime();
-    st_[1] = __builtin_amdgcn_s_memtime();
-#endif
     const int nbm = (p.M + 64 * RT - 1) / (64 * RT);
     const int npanel = (p.N + 15) / 16;
     const int ngrp = (npanel + p.nc - 1) / p.nc;
@@ -532,9 +519,6 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
         }
     };
 
-#ifdef FGR_RS_STAMP
-    st_[2] = __builtin_amdgcn_s_memtime();
-#endif
     if constexpr (PPS == 1) {
         float4 rcur[RT];
         f32x4 prev[RT];
@@ -553,10 +537,6 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
                                    (q + 1 < np ? PW : 0));
     #endif
             __builtin_amdgcn_s_barrier();                    // every wave's pieces; buffer of q - 1 free
-    #ifdef FGR_RS_STAMP
-            if (q == 0) st_[3] = __builtin_amdgcn_s_memtime();
-            if (q == np - 1) st_[4] = __builtin_amdgcn_s_memtime();
-    #endif
             if constexpr (KV)
                 if (kv_pend) kv_finish();                    // block-uniform
             if constexpr (RES)
@@ -602,10 +582,6 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
                 wait_vm_lgkm0_dyn(cnt);
             }
             __builtin_amdgcn_s_barrier();                    // every wave's pieces; stage st - 1's slots free
-#ifdef FGR_RS_STAMP
-            if (st == 0) st_[3] = __builtin_amdgcn_s_memtime();
-            if (st == nstage - 1) st_[4] = __builtin_amdgcn_s_memtime();
-#endif
             if constexpr (KV)
                 if (kv_pend) kv_finish();                    // block-uniform
             if constexpr (RES)
@@ -660,13 +636,6 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
             kv_finish();
         }
     }
-#ifdef FGR_RS_STAMP
-    __syncthreads();
-    st_[5] = __builtin_amdgcn_s_memtime();
-    st_[6] = __builtin_amdgcn_s_memrealtime();
-    st_[7] = (unsigned long long)np;
-    if (tid < 8 && blockIdx.x < (1 << 14)) g_rs_stamp[blockIdx.x][tid] = st_[tid];
-#endif
     if constexpr (HEAD) {
         // sum the lane groups' column quads: lanes c, c + 16, c + 32, c + 48 hold one row
 #pragma unroll
@@ -743,32 +712,16 @@ bool gemm_rs_f16x3(const float* A, int64_t lda, const void* W, int ksteps, const
                  head->n_act % 16 != 0))
         return false;
     // row tiles per wave: 2 (W fragments reused twice) unless that leaves too few blocks
-    const char* rte = getenv("FGR_RS_RT");
-    int RT = (rte && rte[0]) ? atoi(rte) : 2;
-    if (RT != 1 && RT != 2) RT = 2;
-    if (ln) RT = 1;
+    const int RT = ln ? 1 : 2;
     const int npanel = (N + 15) / 16;
     const int nbm = (M + 64 * RT - 1) / (64 * RT);
     // panels per block: as few column groups as fill the resident-block slots once (a second,
     // partial round of blocks costs a whole block time; every group re-reads and re-splits its
-    // rows): slots = 256 CUs x blocks per CU (2 at K > 128, 188 VGPRs; 4 below).
-    // FGR_RS_NC overrides (0: ~3 blocks per CU regardless of occupancy)
-    const char* nce = getenv("FGR_RS_NC");
-    int nc;
-    if (nce && nce[0]) {
-        nc = atoi(nce);
-        if (nc <= 0) {
-            const int64_t target = 768;
-            nc = (int)std::max<int64_t>(1, std::min<int64_t>(npanel, ((int64_t)nbm * npanel + target - 1) / target));
-        }
-    } else {
-        // (the LN prologue at RT 1: 256 / 190 VGPRs at ksteps 8 / 6 -> 2 blocks per CU, 4 below)
-        const int slots = ln ? 256 * (ksteps > 4 ? 2 : 4)
-                             : 256 * (ksteps > 4 ? 2 : 4) * (RT == 1 ? 2 : 1);
-        const int ngrp = std::max(1, slots / std::max(nbm, 1));
-        nc = (npanel + ngrp - 1) / ngrp;
-    }
-    nc = std::min(std::min(nc, npanel), kRsMaxNc);
+    // rows): slots = 256 CUs x blocks per CU (2 at K > 128, 188 VGPRs; 4 below;
+    // the LN prologue at RT 1: 256 / 190 VGPRs at ksteps 8 / 6 -> 2 blocks per CU, 4 below)
+    const int slots = 256 * (ksteps > 4 ? 2 : 4);
+    const int ngrp0 = std::max(1, slots / std::max(nbm, 1));
+    int nc = std::min(std::min((npanel + ngrp0 - 1) / ngrp0, npanel), kRsMaxNc);
     if (head && head->out3) nc = npanel;              // the 3-wide head needs whole rows
     if (ln && ln->kv_img) {
         // K / V images: head dim 32 (two panels per head, never split between blocks), the
@@ -797,11 +750,3 @@ bool gemm_rs_f16x3(const float* A, int64_t lda, const void* W, int ksteps, const
 }
 
 }  // namespace fgr
-
-#ifdef FGR_RS_STAMP
-extern "C" int fgr_debug_rs_stamps(void* dst, int32_t nblocks) {
-    if (nblocks > (1 << 14)) nblocks = 1 << 14;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_rs_stamp), (size_t)nblocks * 64, 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif

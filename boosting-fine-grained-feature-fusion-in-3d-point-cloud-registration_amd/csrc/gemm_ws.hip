@@ -29,12 +29,6 @@
 // Precision: as gemm_rs.hip (one scale per activation row, three fp16 products per product).
 #include "mfma.h"
 
-#ifdef FGR_WS_STAMP
-// Diagnostic build only (tools/ws_bench.py): per (block, wave) s_memtime stamps: [0] entry,
-// [1] after the prologue barrier, [2 + 2 p] pass p's MFMA loop done, [3 + 2 p] its epilogue done,
-// [7] (one pass) the wave's stores complete
-__device__ unsigned long long g_ws_stamp[2048][4][8];
-#endif
 
 namespace fgr {
 namespace {
@@ -105,10 +99,6 @@ gemm_ws_kernel(WsArgs p) {
     constexpr bool kSideLds = LNM == 3 && NPART == 1;
     __shared__ float4 side[kSideLds ? BR * 64 : 1];
 
-#ifdef FGR_WS_STAMP
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    st_[0] = __builtin_amdgcn_s_memtime();
-#endif
     const int nblk = (p.M + BR - 1) / BR * NPART;
     int t = blockIdx.x;
     {   // XCD-aware order: each XCD a contiguous range of (row block, part)
@@ -275,9 +265,6 @@ gemm_ws_kernel(WsArgs p) {
     // LDS writes done, no vector-memory wait (the weight groups stay in flight)
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();
-#ifdef FGR_WS_STAMP
-    st_[1] = __builtin_amdgcn_s_memtime();
-#endif
 
     // 2. the wave's panels, 4 per pass; k32 group G = pass * 8 + s loads W (panel, s, term)
     auto read_act = [&](int s, u32x4 (&f)[2 * RT]) {
@@ -330,9 +317,6 @@ gemm_ws_kernel(WsArgs p) {
             __builtin_amdgcn_sched_group_barrier(0x008, 12 * RT, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#ifdef FGR_WS_STAMP
-        if (pass < 3) st_[2 + 2 * pass] = __builtin_amdgcn_s_memtime();
-#endif
         // 3. the pass's finished values (no stores): lane holds rows r0 + 16 rt + c, columns
         //    col0 + 16 pp + 4 g .. + 3
         if (pass == 0)
@@ -395,9 +379,6 @@ gemm_ws_kernel(WsArgs p) {
                 }
             }
         }
-#ifdef FGR_WS_STAMP
-        if (pass < 3) st_[3 + 2 * pass] = __builtin_amdgcn_s_memtime();
-#endif
     }
 
     // 4. every store of the block
@@ -495,24 +476,15 @@ gemm_ws_kernel(WsArgs p) {
             if (rr < p.M) *reinterpret_cast<float4*>(p.out2 + (int64_t)rr * p.ld_out2 + 4 * (u & 63)) = side[u];
         }
     }
-#ifdef FGR_WS_STAMP
-    __builtin_amdgcn_s_waitcnt(0);
-    if (NPASS == 1) st_[7] = __builtin_amdgcn_s_memtime();    // every store of the wave done
-    if (lane < 8 && blockIdx.x < 2048) g_ws_stamp[blockIdx.x][wv][lane] = st_[lane];
-#endif
 }
 
 // row tiles per block: 3 (48-row blocks) where they fit the CUs in one round and 64-row
 // blocks leave CUs idle (ModelNet's 9544 rows: 199 blocks instead of 150), else 4; the K / V
-// image epilogue writes whole 64-row tiles (4 only). FGR_WS_RT overrides (A/B).
+// image epilogue writes whole 64-row tiles (4 only).
 constexpr int kCusWs = 256;
 template <int NPW, int LNM, bool KV, bool RES, int ACT, int NPART = 1>
 void launch_ws(const WsArgs& a, hipStream_t st) {
-    static const int rt_env = [] { const char* e = getenv("FGR_WS_RT"); return e ? atoi(e) : 0; }();
-    int rt = (rt_env >= 3 && rt_env <= 4) ? rt_env
-             : ((a.M + 47) / 48 <= kCusWs && (a.M + 63) / 64 < kCusWs) ? 3 : 4;
-    if (KV) rt = 4;
-    if (rt == 3)
+    if (!KV && (a.M + 47) / 48 <= kCusWs && (a.M + 63) / 64 < kCusWs)
         hipLaunchKernelGGL((gemm_ws_kernel<NPW, LNM, KV, RES, ACT, KV ? 4 : 3, NPART>),
                            dim3((unsigned)((a.M + 47) / 48 * NPART)), dim3(256), 0, st, a);
     else
@@ -523,15 +495,13 @@ void launch_ws(const WsArgs& a, hipStream_t st) {
 }  // namespace
 
 // The ws kernel's shapes: K = 256, N = 256 (out_proj) or 768 (in_proj), many rows; operands
-// 16-B aligned (checked by the caller). FGR_GEMM_WS=0 disables it (the rs kernel then).
+// 16-B aligned (checked by the caller).
 bool gemm_ws_supported(int m, int n, int k) {
-    static const bool on = [] { const char* e = getenv("FGR_GEMM_WS"); return !(e && e[0] == '0'); }();
-    if (!on || k != 256 || m < 4096) return false;
+    if (k != 256 || m < 4096) return false;
     // N = 512 / 1024: the columns over N / 256 blocks per row tile (ModelNet's 9544 x 512 x 256:
     // 22.2-22.9 -> 19.4-19.6 us; 9544 x 1792 x 256 measured equal to the row-stationary kernel
-    // and left there, profiles/r06_ws_wide_ab.txt); FGR_GEMM_WSN=0 keeps them off (A/B)
-    static const bool wide = [] { const char* e = getenv("FGR_GEMM_WSN"); return !(e && e[0] == '0'); }();
-    return n == 256 || n == 768 || (wide && (n == 512 || n == 1024));
+    // and left there, profiles/r06_ws_wide_ab.txt)
+    return n == 256 || n == 768 || n == 512 || n == 1024;
 }
 
 bool gemm_ws_ln_supported(int m, int n, int k) {
@@ -573,16 +543,11 @@ bool gemm_ws_f16x3(const float* A, int64_t lda, const void* W, const float* wsc,
         if (ln->kv_img) {
             if (relu || !ln->add || ln->n_head * 64 + ln->kv_col0 != N || ln->kv_col0 != 256) return false;
             // without the side output: q | k | v over three blocks per row tile (450 blocks at
-            // ModelNet's 9544 rows, two resident per CU; 28.2 -> 25.3 us), unless FGR_WS_SPLIT=0.
+            // ModelNet's 9544 rows, two resident per CU; 28.2 -> 25.3 us).
             // With it (its 64 KB LDS staging: one block per CU) one block per row tile (31.3 us
             // vs 35.6 split; profiles/r06_ws_split_ab.txt)
-            static const bool split = [] { const char* e = getenv("FGR_WS_SPLIT"); return !(e && e[0] == '0'); }();
-            static const bool split3 = [] { const char* e = getenv("FGR_WS_SPLIT3"); return !(e && e[0] == '0'); }();
-            if (ln->out2) {
-                if (split && split3) launch_ws<4, 3, true, false, FGR_ACT_NONE, 3>(a, st);
-                else launch_ws<12, 3, true, false, FGR_ACT_NONE>(a, st);
-            } else if (split) launch_ws<4, 2, true, false, FGR_ACT_NONE, 3>(a, st);
-            else launch_ws<12, 2, true, false, FGR_ACT_NONE>(a, st);
+            if (ln->out2) launch_ws<4, 3, true, false, FGR_ACT_NONE, 3>(a, st);
+            else launch_ws<4, 2, true, false, FGR_ACT_NONE, 3>(a, st);
             return true;
         }
         if (relu) return false;
@@ -604,11 +569,3 @@ bool gemm_ws_f16x3(const float* A, int64_t lda, const void* W, const float* wsc,
 }
 
 }  // namespace fgr
-
-#ifdef FGR_WS_STAMP
-extern "C" int fgr_debug_ws_stamps(void* dst, int32_t nblocks) {
-    if (nblocks > 2048) nblocks = 2048;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_ws_stamp), (size_t)nblocks * 4 * 8 * 8, 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -148,8 +148,7 @@ int launch_scan(int* io, int* ord, const int64_t* n_dev, int64_t n_max, int2* ti
     const int nt = scan_tiles(n_max);
     hipLaunchKernelGGL(scan_tile_kernel<DUAL>, dim3(nt), dim3(kSB), 0, st, io, n_dev, n_max, tiles);
     FGR_CHECK_LAUNCH("scan_tile_kernel");
-    static const bool two = [] { const char* e = getenv("FGR_SCAN2"); return !(e && e[0] == '0'); }();
-    if (two && nt <= kSB) {                                 // <= 1M counters: two launches
+    if (nt <= kSB) {                                 // <= 1M counters: two launches
         hipLaunchKernelGGL((scan_final_kernel<DUAL, true>), dim3(nt), dim3(kSB), 0, st, io, ord, n_dev,
                            n_max, tiles);
         FGR_CHECK_LAUNCH("scan_final_kernel");

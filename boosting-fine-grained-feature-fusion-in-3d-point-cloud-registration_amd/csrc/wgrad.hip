@@ -296,6 +296,8 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 
 // chunks of rows per output tile: about two workgroups per CU (512) over the tiles, at least
 // 32 rows each, and no more partial bytes than the two operands' bytes
+constexpr int64_t kWgradWgs = 512;          // workgroup target
+constexpr double kWgradPartRatio = 1.0;     // partial / operand bytes cap
 struct WgradPlan {
     int64_t kc;
     int chunks;
@@ -304,19 +306,11 @@ struct WgradPlan {
 };
 
 WgradPlan wgrad_plan(int64_t rows, int m, int n) {
-    static const int64_t target = [] {           // FGR_WGRAD_WGS: workgroup target (A/B)
-        const char* e = getenv("FGR_WGRAD_WGS");
-        return (int64_t)(e ? std::max(1, atoi(e)) : 512);
-    }();
     WgradPlan pl;
     pl.tiles_n = (int)ceil_div(n, kWgT);
     pl.tiles = (int)ceil_div(m, kWgT) * pl.tiles_n;
-    static const double part_ratio = [] {       // FGR_WGRAD_PART: partial / operand bytes cap
-        const char* e = getenv("FGR_WGRAD_PART");
-        return e ? std::max(0.01, atof(e)) : 1.0;
-    }();
-    int64_t ch = ceil_div(target, pl.tiles);
-    ch = std::min(ch, std::max<int64_t>(1, (int64_t)(part_ratio * (double)(rows * (m + n)) /
+    int64_t ch = ceil_div(kWgradWgs, pl.tiles);
+    ch = std::min(ch, std::max<int64_t>(1, (int64_t)(kWgradPartRatio * (double)(rows * (m + n)) /
                                                      ((double)m * n))));
     ch = std::max<int64_t>(1, std::min(ch, ceil_div(rows, kWgK)));
     pl.kc = std::max<int64_t>(kWgK, ceil_div(ceil_div(rows, ch), kWgK) * kWgK);

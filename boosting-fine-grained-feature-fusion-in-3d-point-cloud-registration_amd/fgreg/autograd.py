@@ -29,7 +29,6 @@ Elementwise glue between them (ReLU masks, the bottleneck's LeakyReLU(x + shortc
 concatenation) is torch on the same device. No CPU path: every op raises on host tensors.
 """
 import math
-import os
 
 import torch
 import torch.nn.functional as F
@@ -54,10 +53,6 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-_WGRAD = os.environ.get('FGREG_WGRAD', '1') != '0'     # 0: dW on the generic GEMM (A/B)
-_ATTN_LSE = os.environ.get('FGREG_ATTN_LSE', '1') != '0'  # 0: the backward recomputes it (A/B)
-
-
 def _wgrad_ok(t):
     return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
 
@@ -70,7 +65,7 @@ def wgrad(a: torch.Tensor, b: torch.Tensor, bias_grad=False):
     (transposed) weight image, and fgr_colsum."""
     rows, m = a.shape
     n = b.shape[1]
-    if not (_WGRAD and lin.MODE == 'f16x3'):
+    if lin.MODE != 'f16x3':
         dw = linear(a.t().contiguous(), b, transpose=True, cache=False)
         return (dw, colsum(a.contiguous())) if bias_grad else dw
     if m % 4 or n % 4:
@@ -410,7 +405,7 @@ class _AttentionFn(torch.autograd.Function):
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
         # the forward's log2-sum-exp per (row, head) for the backward (fgr_attention_*_train)
         lse = (torch.empty((qkv.shape[0], nhead), dtype=torch.float32, device=qkv.device)
-               if _ATTN_LSE and ops.attention_lse_ok(q, k, v, nhead) else None)
+               if ops.attention_lse_ok(q, k, v, nhead) else None)
         o = ops.attention(q, k, v, off, off, kv_seg, max_len, nhead,
                           dropout=(seed, p) if p > 0.0 else None, lse=lse)
         ctx.meta = (d, int(max_len), int(nhead), float(p), int(seed))

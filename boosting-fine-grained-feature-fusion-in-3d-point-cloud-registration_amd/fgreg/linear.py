@@ -12,7 +12,6 @@ Weight images are built once and cached against the fp32 tensor's identity, data
 and version (a checkpoint load, .to() or in-place update invalidates the cache). There is no
 library / PyTorch GEMM fallback: a shape the kernels reject raises.
 """
-import os
 
 import numpy as np
 import torch
@@ -84,7 +83,6 @@ def _valid(ent, w):
 # fgr_split_desc (include/fgreg.h): w, img, stride_n, stride_k, panel0, n, k
 _DESC = np.dtype([('w', '<u8'), ('img', '<u8'), ('sn', '<i8'), ('sk', '<i8'), ('panel0', '<i8'),
                   ('n', '<i4'), ('k', '<i4')])
-BATCH_REFRESH = os.environ.get('FGREG_SPLIT_BATCH', '1') != '0'
 
 
 def _refresh_stale(device):
@@ -123,7 +121,7 @@ def weight_image(w: torch.Tensor, transpose=False, tag=None, mode=None, cache=Tr
     mode = mode or MODE
     ck = (id(w), transpose, tag, mode, rows)
     ent = _CACHE.get(ck) if cache else None
-    if (BATCH_REFRESH and ent is not None and mode == 'f16x3' and ent.src is w
+    if (ent is not None and mode == 'f16x3' and ent.src is w
             and ent.ptr == w.data_ptr() and ent.version != w._version and ent.view is not None):
         _refresh_stale(w.device)          # this image and every other stale one, one launch
     if not _valid(ent, w):
@@ -202,8 +200,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias=None, act=ACT_NONE, residual=N
     return out
 
 
-# fgr_gemm_f16x3_ln where supported (False, or FGR_LN_FUSE=0: layernorm, then linear)
-LN_FUSE = os.environ.get('FGR_LN_FUSE', '1') != '0'
+# fgr_gemm_f16x3_ln where supported (False: layernorm, then linear)
+LN_FUSE = True
 
 
 def ln_fusable(m, n, k) -> bool:

@@ -8,7 +8,6 @@ libfgreg.so, these raise.
 """
 import ctypes
 import math
-import os
 from typing import Sequence, Tuple
 
 import torch
@@ -107,9 +106,8 @@ def _end(name, start, work=None):
 
 
 # the current stream's raw handle without building a torch.cuda.Stream object per launch (the
-# eager training step calls this ~1500 times; FGREG_RAW_STREAM=0: torch.cuda.current_stream, A/B)
-_raw_stream = (getattr(torch._C, '_cuda_getCurrentRawStream', None)
-               if os.environ.get('FGREG_RAW_STREAM', '1') != '0' else None)
+# eager training step calls this ~1500 times); a torch without it: torch.cuda.current_stream
+_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
 _cur_dev = getattr(torch._C, '_cuda_getDevice', None)
 
 
@@ -274,7 +272,7 @@ def lengths_to_offsets(len_dev: torch.Tensor) -> torch.Tensor:
 
 # Radius search over a cell grid for clouds of at least this many supports (below it the
 # brute-force index-order scan is faster: fewer launches, the cloud stays in L1/L2).
-GRID_MIN_SUPPORTS = int(os.environ.get('FGREG_RADIUS_GRID_MIN', '4096'))
+GRID_MIN_SUPPORTS = 4096
 GRID_MAX_WIDTH = 256
 
 
@@ -619,9 +617,8 @@ def res2net_chain(h, w, scale, w_frag, bias, x, cat, w_scale=None):
 # split-fp16 MFMA, default) or, in the 'bf16' mode (the BASELINE configs[4] compute mode, set
 # together with linear.MODE by set_precision), fgr_attention_bf16 -- one bf16 product per fp32
 # product. Any other head_dim (4, 8, 16, 128, 256) or unaligned operand: fgr_attention (fp32
-# MFMA). FGREG_ATTN = f16x3 | bf16 overrides the attention mode alone (profiling A/B switch).
-ATTN_MODE = os.environ.get('FGREG_ATTN', 'f16x3')
-assert ATTN_MODE in ('f16x3', 'bf16'), ATTN_MODE
+# MFMA). ATTN_MODE = 'f16x3' | 'bf16' sets the attention mode alone.
+ATTN_MODE = 'f16x3'
 
 
 def attention(q, k, v, q_off, kv_off, kv_seg, max_q_len, n_head, out=None,
@@ -869,13 +866,13 @@ def qkv_attention(h, w_img, bias, q_off, kv_seg, max_len, n_head, mode='f16x3'):
     return o
 
 
-FFN_FUSE = os.environ.get('FGREG_FFN_FUSE', '1') != '0'
+FFN_FUSE = True
 
 
 def ffn_supported(m, d, f, act=ACT_RELU) -> bool:
     """True if the pre-norm feed-forward sub-layer of an (m, d) input with hidden width f and
     activation act (ACT_RELU or ACT_GELU) runs as one launch (fgr_ffn_f16x3_act: d = 256, the
-    ModelNet transformer; GELU: f % 128 == 0 as well; FGREG_FFN_FUSE=0 off)."""
+    ModelNet transformer; GELU: f % 128 == 0 as well; FFN_FUSE False: off)."""
     return FFN_FUSE and bool(_lib.load().fgr_ffn_f16x3_act_supported(m, d, f, act))
 
 

@@ -15,7 +15,7 @@ core (the 20k-point workloads). depth = 1 is the one-ahead pipeline.
 Graph replays clone their outputs (fgreg.regtr._CoreGraph.run), so an output stays valid
 while the next core runs.
 
-``streams`` core streams (default 2, FGREG_PIPE_STREAMS): core i runs on core stream
+``streams`` core streams (default 2): core i runs on core stream
 i mod streams (dedicated streams; streams = 1: the current stream), each replaying its own instance of
 the shape signature's HIP graph (RegTR._forward(slot=...)), so consecutive cores overlap on
 the GPU: the drain / ramp of every one of a core's ~300 dependent launches (a few us each)
@@ -40,7 +40,6 @@ Ordering contract (no extra synchronisation needed by the caller):
     the cores overlap. The core streams are registered in ops.STATE_READERS while the
     pipeline runs, so an in-place weight-image refresh waits for their forwards.
 """
-import os
 from collections import deque
 
 import torch
@@ -48,8 +47,8 @@ import torch
 from . import ops
 from .regtr import RegTR
 
-DEPTH = int(os.environ.get('FGREG_PIPE_DEPTH', '2'))
-STREAMS = int(os.environ.get('FGREG_PIPE_STREAMS', '2'))
+DEPTH = 2
+STREAMS = 2
 
 
 def _meta_tensors(meta):
@@ -88,8 +87,8 @@ def _out_tensors(out):
 def pipeline(model: RegTR, batches, depth=None, streams=None):
     """Yields model(batch) for each batch of ``batches`` (an iterable of forward() batch
     dicts on one device), preprocessing later batches while earlier cores run (``depth``
-    cores in flight ahead of the yielded output; default DEPTH = FGREG_PIPE_DEPTH or 2) on
-    ``streams`` core streams (default STREAMS = FGREG_PIPE_STREAMS or 2)."""
+    cores in flight ahead of the yielded output; default DEPTH) on ``streams`` core streams
+    (default STREAMS)."""
     if model.training and torch.is_grad_enabled():
         raise NotImplementedError('fgreg.pipeline is inference only (eval() / no_grad)')
     depth = max(1, int(DEPTH if depth is None else depth))

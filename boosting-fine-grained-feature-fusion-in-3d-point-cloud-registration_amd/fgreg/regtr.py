@@ -30,11 +30,11 @@ from .transformer import (PositionEmbeddingCoordsSine, PositionEmbeddingLearned,
 _logger = logging.getLogger(__name__)
 
 # compute mode of the correspondence head's GEMMs when the forward runs in bf16 (None: bf16
-# like the rest); FGREG_BF16_HEAD=f16x3 keeps the pose-sensitive head fp32-accurate
-HEAD_MODE = os.environ.get('FGREG_BF16_HEAD') or None
-# the CorrespondenceRegressor head in two fused launches where supported (FGREG_FUSED_HEAD=0: one
-# GEMM per Linear, for A/B)
-FUSED_HEAD = os.environ.get('FGREG_FUSED_HEAD', '1') != '0'
+# like the rest); 'f16x3' keeps the pose-sensitive head fp32-accurate
+HEAD_MODE = None
+# the CorrespondenceRegressor head in two fused launches where supported (False: one GEMM per
+# Linear)
+FUSED_HEAD = True
 
 
 class CorrespondenceRegressor(nn.Module):

@@ -23,16 +23,9 @@ import copy
 import torch
 import torch.nn as nn
 
-import os
-
 from . import linear as lin
 from . import ops
 from .linear import linear, linear_ln, ln_fusable
-
-# the pre-norm in_proj writes the attention's K / V images itself where supported
-# (fgr_gemm_f16x3_ln_qkv; FGREG_QKV_IMAGES=0: fp32 q | k | v and the attention's own image launch)
-QKV_IMAGES = os.environ.get('FGREG_QKV_IMAGES', '1') != '0'
-
 
 class Segments:
     """Device-side segment tables of one packed batch of 2B clouds (built before any graph
@@ -121,7 +114,7 @@ class TransformerCrossEncoderLayer(nn.Module):
             d = x.shape[1]
             # the image path forms norm(x) + pos in its prologue: it needs the pos rows
             # (transformer_encoder_has_pos_emb False -> pos None -> linear_ln below)
-            if (QKV_IMAGES and lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3' and pos is not None
+            if (lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3' and pos is not None
                     and ops.ln_qkv_supported(x.shape[0], d, self.nhead)
                     and (side is None or side[0].eps == norm.eps)):
                 # k / v straight into the attention's images (no fp32 k / v, no image launch)
@@ -131,12 +124,12 @@ class TransformerCrossEncoderLayer(nn.Module):
             q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
             return ops.attention(q, k, v, seg.off, seg.off, kv_seg, seg.max_len, self.nhead)
         d = h_pos.shape[1]
-        if (val_has_pos and QKV_IMAGES and lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3'
+        if (val_has_pos and lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3'
                 and ops.qkv_supported(h_pos.shape[0], d, self.nhead)):
             # head dim 64: the in_proj writes the attention's K / V images itself
             return ops.qkv_attention(h_pos, lin.weight_image(W, mode='f16x3'), b, seg.off, kv_seg,
                                      seg.max_len, self.nhead)
-        if (val_has_pos and QKV_IMAGES and lin.MODE == 'bf16' and ops.ATTN_MODE == 'bf16'
+        if (val_has_pos and lin.MODE == 'bf16' and ops.ATTN_MODE == 'bf16'
                 and ops.qkv_bf16_supported(h_pos.shape[0], d, self.nhead)):
             return ops.qkv_attention(h_pos, lin.weight_image(W, mode='bf16'), b, seg.off, kv_seg,
                                      seg.max_len, self.nhead, mode='bf16')

@@ -312,8 +312,8 @@ int fgr_gemm_f16x3_ln_out2(const float* x, int64_t ldx, const float* gamma, cons
  * fgr_ffn_f16x3, which calls it) or FGR_ACT_GELU (the exact erf GELU, 0.5 z (1 + erf(z / sqrt
  * 2)), formed on the fp32 hidden value before its fp16 split); any other code is FGR_E_ARG.
  * fgr_ffn_f16x3_act_supported(m, d, f, act): for FGR_ACT_RELU what fgr_ffn_f16x3_supported
- * returns; for FGR_ACT_GELU that and f % 128 == 0 (GELU exists in the default, weight-split
- * kernel only; the FGR_FFN_V environment switch is ignored for it); 0 for any other code.
+ * returns; for FGR_ACT_GELU that and f % 128 == 0 (GELU exists in the weight-split kernel
+ * only); 0 for any other code.
  * Unsupported GELU shapes run as fgr_gemm_f16x3_ln (FGR_ACT_NONE), fgr_gelu_fwd in place, then
  * fgr_gemm_f16x3_ws (residual). */
 int fgr_split_weights_ffn2_bytes(int32_t n, int32_t k, size_t* bytes);

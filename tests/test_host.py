@@ -234,3 +234,30 @@ def test_load_fragment_formats(tmp_path):
     np.savez(os.path.join(tmp_path, 'a.npz'), xyz=a)
     for f in ('a.pth', 'a.npy', 'a.npz'):
         assert np.array_equal(load_fragment(os.path.join(tmp_path, f)), a)
+
+
+# every environment variable the product reads (DESIGN.md "Environment switches"): the tile /
+# split-K forcing of the GEMM tests and tools, the Res2Net variants of the kernel and footprint
+# tests, the unfused segment norm that is a test's reference, and the switches bench.py names
+ENV_SWITCHES = {'FGR_GEMM16_TILE', 'FGR_GEMM_BF16_TILE', 'FGR_GEMM_KSPLIT', 'FGR_R2N_ROWS',
+                'FGREG_R2N224', 'FGR_SEG_FUSED', 'FGREG_GRAPHS', 'FGREG_DIST_BACKEND',
+                'FGREG_LIB_PATH'}
+
+
+def test_environment_switches_are_the_documented_ones():
+    """The FGR_* / FGREG_* names read through getenv("...") in csrc/ and through os.environ /
+    os.getenv in the package and bench.py are exactly ENV_SWITCHES: an A/B of anything else is
+    a second library (tools/build_variant.sh + FGREG_LIB_PATH), not a switch in the product."""
+    import glob
+    pkg = os.path.join(REPO, 'boosting-fine-grained-feature-fusion-in-3d-point-cloud-registration_amd')
+    native = [f for ext in ('hip', 'h', 'cpp') for f in glob.glob(os.path.join(pkg, 'csrc', '*.' + ext))]
+    python = (glob.glob(os.path.join(pkg, '*.py')) + glob.glob(os.path.join(pkg, 'fgreg', '*.py'))
+              + [os.path.join(REPO, 'bench.py')])
+    assert len(native) > 20 and len(python) > 20
+    found = set()
+    for f in native:
+        found.update(re.findall(r'getenv\s*\(\s*"(\w+)"', open(f).read()))
+    for f in python:
+        found.update(re.findall(r'''(?:environ(?:\.get|\.pop|\.setdefault)?\s*[\[(]|getenv\s*\()\s*['"](FGR\w*)['"]''',
+                                open(f).read()))
+    assert found == ENV_SWITCHES, sorted(found ^ ENV_SWITCHES)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B build (CPU side): libfgreg from a scratch copy of csrc/ into ablib/libfgreg_<name>.so,
-# with extra hipcc flags (e.g. -DFGR_RS_NB=4) and optionally the sources of a git ref instead
+# with extra hipcc flags (e.g. -DFGR_RS_LA=2) and optionally the sources of a git ref instead
 # of the working tree. The product objects stay untouched.
 # usage: bash tools/build_variant.sh <name> "<extra hipcc flags>" [git-ref]
 set -e

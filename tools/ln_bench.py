@@ -1,6 +1,6 @@
 """LayerNorm microbenchmark (development tool, GPU): ops.layernorm at the transformer's
-shapes, with the pending bias and the added residual, device time from HIP-graph replays
-(FGR_LN_LPR selects the lanes per row). usage: python tools/ln_bench.py"""
+shapes, with the pending bias and the added residual, device time from HIP-graph replays.
+usage: python tools/ln_bench.py"""
 import os
 import sys
 
@@ -21,12 +21,10 @@ def main():
         pb = torch.randn(d, device=dev)
         g, b = torch.randn(d, device=dev), torch.randn(d, device=dev)
         out = torch.empty(n, d, device=dev)
-        for lpr in ('', '32', '64'):
-            os.environ['FGR_LN_LPR'] = lpr
-            us = timeit(lambda: ops.layernorm(x, g, b, 1e-5, add=add, out=out))
-            us2 = timeit(lambda: ops.layernorm(x, g, b, 1e-5, pre_bias=pb, add=add, out=out))
-            print(f'n={n} d={d} lpr={lpr or "default"}: {us:6.2f} us ({3 * n * d * 4 / us / 1e3:5.0f} GB/s), '
-                  f'with pre-bias {us2:6.2f} us ({4 * n * d * 4 / us2 / 1e3:5.0f} GB/s)', flush=True)
+        us = timeit(lambda: ops.layernorm(x, g, b, 1e-5, add=add, out=out))
+        us2 = timeit(lambda: ops.layernorm(x, g, b, 1e-5, pre_bias=pb, add=add, out=out))
+        print(f'n={n} d={d}: {us:6.2f} us ({3 * n * d * 4 / us / 1e3:5.0f} GB/s), '
+              f'with pre-bias {us2:6.2f} us ({4 * n * d * 4 / us2 / 1e3:5.0f} GB/s)', flush=True)
 
 
 if __name__ == '__main__':

@@ -34,13 +34,6 @@ def main():
         fl.LN_FUSE = True
         print(f'{m}x{n}x{k} pos={pos} act={act} fused={fused}: fused {t_f:6.1f} us | '
               f'layernorm {t_ln:5.1f} + gemm {t_g:5.1f} = {t_ln + t_g:6.1f} us', flush=True)
-        if 'sweep' in sys.argv[1:]:          # W panels per block of the fused launch
-            res = []
-            for nc in (4, 6, 8, 12, 16, 24, 48):
-                os.environ['FGR_RS_NC'] = str(nc)
-                res.append(f'nc{nc} {timeit(lambda: fl.linear_ln(x, norm, w, b, act=act, add=p, out=out)):5.1f}')
-            os.environ.pop('FGR_RS_NC')
-            print('   fused by nc: ' + ' | '.join(res), flush=True)
 
 
 if __name__ == '__main__':

@@ -1,7 +1,6 @@
 """Row-stationary GEMM sweep (development tool, GPU): times fgr_gemm_f16x3 on the forward's
-K <= 256 shapes for the k-looped default (FGR_GEMM_RS=0 behaviour via FGR_GEMM16_TILE of the
-old choice) and the rs kernel at row tiles RT in {1, 2} and panels per block NC, each variant
-checked against an fp64 product.
+K <= 256 shapes for the k-looped choice (FGR_GEMM16_TILE of the old choice) and the rs kernel
+(FGR_GEMM16_TILE=z), each checked against an fp64 product.
 usage: python tools/rs_sweep.py > gpurun_out/rs_sweep.txt"""
 import os
 import sys
@@ -26,7 +25,6 @@ OLD = {(9544, 768, 256): 'y', (9544, 256, 256): 'X', (9544, 1024, 256): 'y',
        (57264, 3, 256): 'X', (57264, 1, 256): 'X', (40000, 128, 256): 'X',
        (2120, 896, 128): 'X', (2120, 1792, 256): 'Y', (26778, 256, 128): 'X',
        (40000, 224, 32): 'X', (26778, 448, 64): 'X', (26778, 64, 256): 'X'}
-VARIANTS = [('2', ''), ('1', ''), ('2', '0'), ('2', '4'), ('2', '8'), ('2', '16')]
 
 
 def main():
@@ -43,18 +41,12 @@ def main():
         us_old = timeit(lambda: lin.linear(x, w, b, out=out))
         line = f'M={M:6d} N={N:5d} K={K:4d} | old {OLD[(M, N, K)]} {us_old:6.1f}us'
         os.environ['FGR_GEMM16_TILE'] = 'z'
-        best = None
-        for rt, nc in VARIANTS:
-            os.environ['FGR_RS_RT'], os.environ['FGR_RS_NC'] = rt, nc
-            y = lin.linear(x, w, b, out=out)
-            err = float((y.double() - ref).abs().max() / ref.abs().max())
-            us = timeit(lambda: lin.linear(x, w, b, out=out))
-            line += f' | rt{rt}/nc{nc or "auto"} {us:6.1f}us{"" if err < 2e-6 else " ERR%.1e" % err}'
-            if best is None or us < best[1]:
-                best = (f'rt{rt}/nc{nc or "auto"}', us)
-        os.environ['FGR_RS_RT'], os.environ['FGR_RS_NC'] = '', ''
+        y = lin.linear(x, w, b, out=out)
+        err = float((y.double() - ref).abs().max() / ref.abs().max())
+        us = timeit(lambda: lin.linear(x, w, b, out=out))
+        line += f' | rs {us:6.1f}us{"" if err < 2e-6 else " ERR%.1e" % err}'
         os.environ['FGR_GEMM16_TILE'] = ''
-        print(line + f' || best {best[0]} {us_old / best[1]:.2f}x', flush=True)
+        print(line + f' || {us_old / us:.2f}x', flush=True)
 
 
 if __name__ == '__main__':

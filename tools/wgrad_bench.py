@@ -1,7 +1,7 @@
 """Per-shape device time of fgreg.autograd.wgrad (fgr_gemm_f16x3_wgrad, dW = dY^T X with the
 bias gradient) on the ModelNet B=8 training step's weight-gradient shapes: 20 calls in one HIP
 graph, replayed 10 times; rate in fp32-equivalent flops (2 rows m n) and against the f16x3 pipe.
-usage: [FGR_WGRAD_WGS=...] python tools/wgrad_bench.py"""
+usage: python tools/wgrad_bench.py"""
 import os
 import sys
 

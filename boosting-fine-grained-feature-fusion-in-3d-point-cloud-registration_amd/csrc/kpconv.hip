@@ -11,7 +11,7 @@
 // HBM-bound. Per query the algorithmic traffic is
 //   8*width (idx row) + 12 (q) + v*(12 + 4*cin) (valid neighbour xyz + feature row)
 //   + 4*K*cin (wf row) + 4 (nnorm),
-// dominated by the wf write. Wide-channel layers (cin % 64 == 0) run one wave per
+// dominated by the wf write. Wide-channel layers (cin 64 / 128 / 256) run one wave per
 // query with channels on lanes (VEC contiguous floats per lane -> 16-B loads/stores);
 // narrow layers (cin < 64) run one thread per (query, kernel point).
 #include "mfma.h"
@@ -478,16 +478,20 @@ extern "C" int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int
                 "fgr_kpconv_gather: bad arguments (cin %d, n_kp %d, width %d)", cin, n_kp, width);
     FGR_REQUIRE(nq == 0 || (q && s && x && kp && wf && nnorm && (idx || width == 0)),
                 "fgr_kpconv_gather: null pointer");
+    FGR_REQUIRE(cin <= 64 || cin == 128 || cin == 256,
+                "fgr_kpconv_gather: cin %d unsupported (need 1..64, 128 or 256)", cin);
     if (nq == 0) return FGR_OK;
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
     const float inv_ext = 1.0f / extent;
-    if (cin % 64 == 0 && cin <= 256) {
-        switch (cin / 64) {
-            case 1: launch_wide_k<1>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st); break;
-            case 2: launch_wide_k<2>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st); break;
-            default: launch_wide_k<4>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st); break;
-        }
+    // the wide kernel bakes cin = 64 * VEC into its row strides and its vector accesses take
+    // VEC in {1, 2, 4}: every other width (192 included) is refused below, never rounded up
+    if (cin == 64) {
+        launch_wide_k<1>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st);
+    } else if (cin == 128) {
+        launch_wide_k<2>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st);
+    } else if (cin == 256) {
+        launch_wide_k<4>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st);
     } else if (cin <= 64) {
         if (cin == 1) {
             const dim3 grid((unsigned)ceil_div(nq * 16, 256));
@@ -511,9 +515,6 @@ extern "C" int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int
         else if (cin <= 16) launch_narrow<16>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
         else if (cin <= 32) launch_narrow<32>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
         else launch_narrow<64>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
-    } else {
-        set_error("fgr_kpconv_gather: cin %d unsupported (need <= 64 or a multiple of 64 <= 256)", cin);
-        return FGR_E_ARG;
     }
     FGR_CHECK_LAUNCH("kpconv_gather");
     return FGR_OK;

@@ -128,6 +128,8 @@ int fgr_radius_search_grid(const float* q, const int64_t* q_off, int32_t n_cloud
  *   wf[q, k, c] = sum_{valid h} max(0, 1 - |(s[idx[q,h]] - q) - kp[k]| / extent) * x[idx[q,h], c]
  * and the normaliser of :395-399: nnorm[q] = max(1, #{valid h : sum_c x[idx[q,h], c] > 0}).
  * The caller finishes with (wf.view(nq, K*cin) @ W.view(K*cin, cout)) / nnorm.
+ * cin: 1..64, 128 or 256; n_kp <= 32. Any other cin (96, 192, ...) returns FGR_E_ARG
+ * before anything is launched or written.
  * workspace: fgr_kpconv_gather_workspace() bytes (per-source-row flags of the normaliser). */
 int fgr_kpconv_gather_workspace(int64_t ns, int32_t cin, size_t* bytes);
 int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int64_t ns, const int64_t* idx,

@@ -84,11 +84,12 @@ def _kpconv_case(cin):
     return q, s, idx, kp, extent, x, W, gk
 
 
-@pytest.mark.parametrize('cin', [1, 16, 32, 64, 128, 256])
+@pytest.mark.parametrize('cin', [1, 3, 12, 16, 24, 32, 48, 64, 128, 256])
 @pytest.mark.parametrize('strided', [False, True])
 def test_kpconv_backward(gpu, cin, strided):
     """kpconv_t (gather + weight GEMM, normalised by the returned nnorm) vs the oracle's KPConv
-    (finegrained_kpconv_blocks.py:265-401 restated) in fp64: dx (fgr_kpconv_scatter) and dW."""
+    (finegrained_kpconv_blocks.py:265-401 restated) in fp64: dx (fgr_kpconv_scatter) and dW; every
+    forward gather kernel family (stem, narrow<8 / 16 / 32 / 64>, quad-lane, wide)."""
     from fgreg.autograd import kpconv_t
     q, s, idx, kp, extent, x0, W0, gk = _kpconv_case(cin)
     if strided:
@@ -274,13 +275,14 @@ def _attn_ref(qkv, lens, kv_seg, nhead):
 _KV_SEG = {'self': [0, 1, 2, 3], 'cross': [2, 3, 0, 1], 'shared': [3, 3, 0, 0]}
 
 
-@pytest.mark.parametrize('d,nhead', [(32, 8), (256, 8), (512, 8)])
+@pytest.mark.parametrize('d,nhead', [(32, 8), (64, 8), (128, 8), (256, 8), (512, 8)])
 @pytest.mark.parametrize('kind', ['self', 'cross', 'shared'])
 def test_attention_backward(gpu, d, nhead, kind):
     """attention_t (fused QKV; self = every cloud to itself, cross = cloud c to (c + B) mod 2B,
     shared = two query clouds on one key cloud: its dK / dV sum over both) vs fp64 softmax
-    attention: dq, dk, dv through fgr_attention_bwd (head dim 4) / fgr_attention_bwd_train
-    (head dims 32 / 64: the f16x3 kernels), unequal lengths incl. a 1-row cloud and clouds past
+    attention: dq, dk, dv through fgr_attention_bwd (head dims 4 and 8: the scalar kernels; 16:
+    the fp32-MFMA kernels) / fgr_attention_bwd_train (head dims 32 / 64: the f16x3 kernels),
+    unequal lengths incl. a 1-row cloud and clouds past
     one 64-row tile."""
     from fgreg import ops
     from fgreg.autograd import attention_t

@@ -34,6 +34,47 @@ def test_python_signatures_cover_header():
     assert syms == set(_lib.SIGNATURES)
 
 
+def _param_class(decl):
+    """The class of one C parameter declaration of include/fgreg.h: pointer, int32, int64,
+    float, size_t or uint32."""
+    decl = ' '.join(decl.replace('const', ' ').split())
+    if '*' in decl:
+        return 'pointer'
+    base = decl.rsplit(' ', 1)[0] if ' ' in decl else decl      # drop the parameter's name
+    return {'int32_t': 'int32', 'int64_t': 'int64', 'float': 'float', 'size_t': 'size_t',
+            'uint32_t': 'uint32', 'int': 'int32'}[base]
+
+
+def _ctypes_class(t):
+    if t is ctypes.c_void_p or t is ctypes.c_char_p or hasattr(t, 'contents') or \
+            (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return 'pointer'
+    return {ctypes.c_int32: 'int32', ctypes.c_int64: 'int64', ctypes.c_float: 'float',
+            ctypes.c_size_t: 'size_t', ctypes.c_uint32: 'uint32'}[t]
+
+
+def test_python_signatures_match_header_prototypes():
+    """Every prototype of include/fgreg.h against the hand-typed fgreg._lib.SIGNATURES: the
+    same number of parameters and, position by position, the same class (pointer, int32, int64,
+    float, size_t, uint32). A parameter typed one class off still loads and still runs; it
+    passes a truncated or misplaced value to the kernel."""
+    from fgreg import _lib
+    src = open(os.path.join(REPO, 'include', 'fgreg.h')).read()
+    src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', ' ', src)
+    protos = re.findall(r'\bint\s+(fgr_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
+    seen = {}
+    for name, params in protos:
+        params = params.strip()
+        seen[name] = [] if params in ('', 'void') else [_param_class(p) for p in params.split(',')]
+    seen.pop('fgr_abi_version', None)
+    assert set(seen) == set(_lib.SIGNATURES), sorted(set(seen) ^ set(_lib.SIGNATURES))
+    assert len(seen) >= 100
+    for name, want in seen.items():
+        got = [_ctypes_class(t) for t in _lib.SIGNATURES[name]]
+        assert got == want, (name, got, want)
+
+
 def test_argument_errors_are_reported_without_gpu():
     import fgreg
     L = fgreg.load()
@@ -47,6 +88,21 @@ def test_argument_errors_are_reported_without_gpu():
     rc = L.fgr_attention(None, 0, None, 0, None, 0, None, 0, None, None, None, 1, 1, 1, 32,
                          ctypes.c_float(1.0), None)
     assert rc == -1
+
+
+def test_gather_width_check_needs_no_gpu():
+    """fgr_kpconv_gather validates cin before it looks at the row count: with nq = 0 (nothing
+    to launch, no pointer needed) 96, 192 and 320 are FGR_E_ARG with the supported widths in
+    the message, and 1, 48, 64, 128 and 256 are accepted."""
+    import fgreg
+    L = fgreg.load()
+    call = lambda cin: L.fgr_kpconv_gather(None, None, 0, 10, None, 4, None, cin, None, 15,
+                                           ctypes.c_float(1.0), None, None, None, 0, None)
+    for cin in (96, 192, 320):
+        assert call(cin) == -1
+        assert f'cin {cin} unsupported (need 1..64, 128 or 256)'.encode() in L.fgr_last_error()
+    for cin in (1, 48, 64, 128, 256):
+        assert call(cin) == 0
 
 
 def test_ops_refuse_cpu_tensors():

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/fgreg.h"
 
@@ -104,13 +105,66 @@ __device__ __forceinline__ int find_segment(const int64_t* off, int n, int64_t r
     return lo;
 }
 
-// KPConv kernel-point influence of a neighbour at (nx, ny, nz): linear in its distance to
-// kernel point k, zero beyond the extent (the forward and its backward)
-__device__ __forceinline__ float kp_weight(float nx, float ny, float nz, const float* kp, int k,
-                                           float inv_extent) {
+// KPConv kernel-point influence of a neighbour at (nx, ny, nz) (the forward and its backward,
+// finegrained_kpconv_blocks.py:347-372). INF and AGG are compile-time FGR_KP_* / FGR_AGG_*
+// values; wscale comes from kp_wscale below.
+__device__ __forceinline__ float kp_d2(float nx, float ny, float nz, const float* kp, int k) {
     float dx = nx - kp[3 * k], dy = ny - kp[3 * k + 1], dz = nz - kp[3 * k + 2];
-    float d2 = dx * dx + dy * dy + dz * dz;
-    return fmaxf(1.0f - sqrtf(d2) * inv_extent, 0.0f);
+    return dx * dx + dy * dy + dz * dz;
+}
+// linear in the distance and zero beyond the extent; a gaussian of sigma 0.3 extent (expf: its
+// error against fp64 is torch's own; the argument reaches the hundreds); or 1
+template <int INF>
+__device__ __forceinline__ float kp_influence(float d2, float wscale) {
+    if constexpr (INF == FGR_KP_LINEAR) return fmaxf(1.0f - sqrtf(d2) * wscale, 0.0f);
+    else if constexpr (INF == FGR_KP_GAUSSIAN) return expf(-d2 * wscale);
+    else return 1.0f;
+}
+template <int INF>
+__device__ __forceinline__ float kp_weight(float nx, float ny, float nz, const float* kp, int k,
+                                           float wscale) {
+    return kp_influence<INF>(kp_d2(nx, ny, nz, kp, k), wscale);
+}
+// FGR_AGG_CLOSEST: only the nearest kernel point (the lowest k on an exact tie, as
+// torch.argmin) keeps its influence. -> that influence, its k in *best_k
+template <int INF>
+__device__ __forceinline__ float kp_closest(float nx, float ny, float nz, const float* kp,
+                                            int n_kp, float wscale, int* best_k) {
+    float best = kp_d2(nx, ny, nz, kp, 0);
+    int bk = 0;
+    // partly unrolled, so that several kernel points' LDS reads can be in flight
+#pragma unroll 4
+    for (int k = 1; k < n_kp; ++k) {
+        const float d2 = kp_d2(nx, ny, nz, kp, k);
+        if (d2 < best) { best = d2; bk = k; }
+    }
+    *best_k = bk;
+    return kp_influence<INF>(best, wscale);
+}
+// The one float the influence needs: 1 / extent (linear), 1 / (2 (0.3 extent)^2 + 1e-9) taken
+// in double (gaussian, radius_gaussian's denominator, :100-107), unused (constant)
+inline float kp_wscale(int influence, float extent) {
+    if (influence != FGR_KP_GAUSSIAN) return 1.0f / extent;
+    const double sig = 0.3 * (double)extent;
+    return (float)(1.0 / (2.0 * sig * sig + 1e-9));
+}
+inline bool kp_modes_ok(int influence, int aggregation) {
+    return influence >= FGR_KP_LINEAR && influence <= FGR_KP_CONSTANT &&
+           (aggregation == FGR_AGG_SUM || aggregation == FGR_AGG_CLOSEST);
+}
+// Calls f(integral_constant<INF>, integral_constant<AGG>) for the run-time pair (checked by
+// kp_modes_ok), so kernels take both as template parameters
+template <class F>
+void kp_with_modes(int influence, int aggregation, F&& f) {
+    using std::integral_constant;
+    switch (influence * 2 + aggregation) {
+        case 0: f(integral_constant<int, 0>{}, integral_constant<int, 0>{}); break;
+        case 1: f(integral_constant<int, 0>{}, integral_constant<int, 1>{}); break;
+        case 2: f(integral_constant<int, 1>{}, integral_constant<int, 0>{}); break;
+        case 3: f(integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
+        case 4: f(integral_constant<int, 2>{}, integral_constant<int, 0>{}); break;
+        default: f(integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
+    }
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

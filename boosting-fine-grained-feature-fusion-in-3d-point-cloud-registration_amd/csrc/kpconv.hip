@@ -3,7 +3,9 @@
 // fgr_kpconv_gather computes, for every query q,
 //   wf[q, k, c] = sum_{valid h} w(q, h, k) * x[idx[q, h], c],
 //   w(q, h, k)  = max(0, 1 - sqrt(|(s[idx[q,h]] - q) - kp[k]|^2) / extent)
-// (finegrained_kpconv_blocks.py:296-381) and the KPConv normaliser
+// (finegrained_kpconv_blocks.py:296-381; fgr_kpconv_gather_mode: the gaussian and constant
+// influences and the closest aggregation of :347-372, compile-time INF / AGG of every kernel
+// here, kp_influence / kp_closest of common.h) and the KPConv normaliser
 //   nnorm[q] = max(1, #{valid h : sum_c x[idx[q, h], c] > 0})            (:395-399).
 // Shadow entries (idx >= ns) carry zero weight and a zero feature row in the
 // reference, so they are skipped here: only valid neighbours are read.
@@ -74,20 +76,61 @@ __device__ __forceinline__ void store_wf(float* p, const float (&v)[VEC]) {
     }
 }
 
+// FGR_AGG_CLOSEST weights of a chunk's v compacted neighbours (centred positions p) ->
+// w[row][k], k < KW: one lane per row walks the K distances for the running minimum and writes
+// the row's K masked weights with 16-B stores (the kernels align w to 16 B); a chunk has
+// at most 64 rows, so this is one pass. Pad rows get 0 from a store of their own and the
+// columns k >= n_kp get 0, as in the sum loops of the kernels. At these sizes the kernels are
+// bound by instruction issue as much as by memory, and a wave pays for every instruction of
+// the stage whatever the number of rows, so the stage is kept short.
+template <int KW, int U, int INF>
+__device__ __forceinline__ void chunk_weights_closest(float (&w)[64 + U][KW], const float3* p,
+                                                      int v, int lane, const float* kp, int n_kp,
+                                                      float wscale) {
+    static_assert(KW % 4 == 0, "16-B stores");
+    for (int t = lane; t < U * KW; t += 64) w[v + t / KW][t % KW] = 0.f;
+    for (int hh = lane; hh < v; hh += 64) {
+        const float3 d = p[hh];
+        int bk;
+        float wb;
+        if constexpr (KW <= 16) {
+            // every kernel point of the (3 * kMaxKp float) LDS copy is read up front, the
+            // ones past n_kp masked: the run-time walk of kp_closest waits for one LDS
+            // round trip per kernel point
+            float best = kp_d2(d.x, d.y, d.z, kp, 0);
+            bk = 0;
+#pragma unroll
+            for (int k = 1; k < KW; ++k) {
+                const float t = kp_d2(d.x, d.y, d.z, kp, k);
+                const float d2 = k < n_kp ? t : INFINITY;
+                if (d2 < best) { best = d2; bk = k; }
+            }
+            wb = kp_influence<INF>(best, wscale);
+        } else {
+            wb = kp_closest<INF>(d.x, d.y, d.z, kp, n_kp, wscale, &bk);
+        }
+#pragma unroll
+        for (int k = 0; k < KW; k += 4)
+            *reinterpret_cast<float4*>(&w[hh][k]) =
+                make_float4(k == bk ? wb : 0.f, k + 1 == bk ? wb : 0.f, k + 2 == bk ? wb : 0.f,
+                            k + 3 == bk ? wb : 0.f);
+    }
+}
+
 // One wave per query, cin = 64 * VEC, K kernel points (runtime, <= kMaxKp, unrolled by KU).
 // Valid neighbours of each 64-wide chunk are compacted by ballot; their feature rows are
 // then streamed 4 at a time (4 x 16-B loads in flight per lane) into K accumulators.
 // POSI: the normaliser's "row sum > 0" is taken from the rows as they stream by (a DPP /
 // permlane wave sum per row, no LDS); otherwise from per-source-row flags `pos`.
-template <int VEC, int KU, bool POSI>
+template <int VEC, int KU, bool POSI, int INF, int AGG>
 __global__ void __launch_bounds__(64 * kGatherWaves)
 kpconv_gather_wide(const float* __restrict__ q, const float* __restrict__ s, int64_t nq, int64_t ns,
                    const int64_t* __restrict__ idx, int width, const float* __restrict__ x,
                    const unsigned char* __restrict__ pos, const float* __restrict__ kp_g, int n_kp,
-                   float inv_extent, float* __restrict__ wf, float* __restrict__ nnorm) {
+                   float wscale, float* __restrict__ wf, float* __restrict__ nnorm) {
     constexpr int CIN = 64 * VEC;
     constexpr int U = GATHER_U;                        // neighbour rows in flight
-    __shared__ float w_lds[kGatherWaves][64 + U][KU];
+    __shared__ __attribute__((aligned(16))) float w_lds[kGatherWaves][64 + U][KU];
     __shared__ int nb_lds[kGatherWaves][64 + U];
     __shared__ float3 p_lds[kGatherWaves][64];
     __shared__ float kp[3 * kMaxKp];
@@ -133,14 +176,20 @@ kpconv_gather_wide(const float* __restrict__ q, const float* __restrict__ s, int
         for (int u = 0; u < U; ++u)
             load_vec<VEC>(x + (int64_t)nb_lds[wv][u] * CIN + lane * VEC, xn[u]);
         // kernel-point influences of the valid neighbours -> LDS (pad rows get 0)
-        for (int t = lane; t < (v + U) * KU; t += 64) {
-            const int hh = t / KU, k = t - hh * KU;
-            float w = 0.f;
-            if (hh < v && k < n_kp) {
-                const float3 d = p_lds[wv][hh];
-                w = kp_weight(d.x, d.y, d.z, kp, k, inv_extent);
+        // (pad rows and k >= n_kp get 0 in EVERY mode: the accumulate loop multiplies pad rows
+        // with feature row 0, and a constant influence taken from the function would add x[0])
+        if constexpr (AGG == FGR_AGG_CLOSEST) {
+            chunk_weights_closest<KU, U, INF>(w_lds[wv], p_lds[wv], v, lane, kp, n_kp, wscale);
+        } else {
+            for (int t = lane; t < (v + U) * KU; t += 64) {
+                const int hh = t / KU, k = t - hh * KU;
+                float w = 0.f;
+                if (hh < v && k < n_kp) {
+                    const float3 d = p_lds[wv][hh];
+                    w = kp_weight<INF>(d.x, d.y, d.z, kp, k, wscale);
+                }
+                w_lds[wv][hh][k] = w;
             }
-            w_lds[wv][hh][k] = w;
         }
         __builtin_amdgcn_wave_barrier();
         for (int hh = 0; hh < v; hh += U) {
@@ -197,15 +246,15 @@ kpconv_gather_wide(const float* __restrict__ q, const float* __restrict__ s, int
 // points k = kg, kg + KG, .... Valid neighbours are compacted by ballot and their K kernel-
 // point influences computed once into LDS (as kpconv_gather_wide); the row-sum positivity
 // of the normaliser is a DPP reduction over the QUADS lanes that hold the row.
-template <int QUADS, int KPL>
+template <int QUADS, int KPL, int INF, int AGG>
 __global__ void __launch_bounds__(256)
 kpconv_gather_quads(const float* __restrict__ q, const float* __restrict__ s, int64_t nq,
                     int64_t ns, const int64_t* __restrict__ idx, int width,
                     const float* __restrict__ x, const float* __restrict__ kp_g, int n_kp,
-                    float inv_extent, float* __restrict__ wf, float* __restrict__ nnorm) {
+                    float wscale, float* __restrict__ wf, float* __restrict__ nnorm) {
     constexpr int CIN = 4 * QUADS, KG = 64 / QUADS, U = GATHER_U, KW = 16;
     static_assert(KG * KPL >= KW, "kernel points per lane");
-    __shared__ float w_lds[4][64 + U][KW];
+    __shared__ __attribute__((aligned(16))) float w_lds[4][64 + U][KW];
     __shared__ int nb_lds[4][64 + U];
     __shared__ float3 p_lds[4][64];
     __shared__ float kp[3 * kMaxKp];
@@ -235,14 +284,19 @@ kpconv_gather_quads(const float* __restrict__ q, const float* __restrict__ s, in
         }
         if (lane < U) nb_lds[wv][v + lane] = 0;        // pad rows: weight 0, row 0
         __builtin_amdgcn_wave_barrier();
-        for (int t = lane; t < (v + U) * KW; t += 64) {
-            const int hh = t / KW, k = t % KW;
-            float w = 0.f;
-            if (hh < v && k < n_kp) {
-                const float3 d = p_lds[wv][hh];
-                w = kp_weight(d.x, d.y, d.z, kp, k, inv_extent);
+        // pad rows and k >= n_kp: weight 0 in every mode (kpconv_gather_wide)
+        if constexpr (AGG == FGR_AGG_CLOSEST) {
+            chunk_weights_closest<KW, U, INF>(w_lds[wv], p_lds[wv], v, lane, kp, n_kp, wscale);
+        } else {
+            for (int t = lane; t < (v + U) * KW; t += 64) {
+                const int hh = t / KW, k = t % KW;
+                float w = 0.f;
+                if (hh < v && k < n_kp) {
+                    const float3 d = p_lds[wv][hh];
+                    w = kp_weight<INF>(d.x, d.y, d.z, kp, k, wscale);
+                }
+                w_lds[wv][hh][k] = w;
             }
-            w_lds[wv][hh][k] = w;
         }
         __builtin_amdgcn_wave_barrier();
         for (int hh = 0; hh < v; hh += U) {
@@ -282,12 +336,12 @@ kpconv_gather_quads(const float* __restrict__ q, const float* __restrict__ s, in
 }
 
 // One thread per (query, kernel point); cin <= 64 (narrow layers, incl. the cin = 1 stem).
-template <int CMAX>
+template <int CMAX, int INF, int AGG>
 __global__ void __launch_bounds__(256)
 kpconv_gather_narrow(const float* __restrict__ q, const float* __restrict__ s, int64_t nq,
                      int64_t ns, const int64_t* __restrict__ idx, int width,
                      const float* __restrict__ x, int cin, const float* __restrict__ kp_g,
-                     int n_kp, float inv_extent, float* __restrict__ wf,
+                     int n_kp, float wscale, float* __restrict__ wf,
                      float* __restrict__ nnorm) {
     __shared__ float kp[3 * kMaxKp];
     for (int i = threadIdx.x; i < 3 * n_kp; i += blockDim.x) kp[i] = kp_g[i];
@@ -306,7 +360,15 @@ kpconv_gather_narrow(const float* __restrict__ q, const float* __restrict__ s, i
         const int64_t id = row[h];
         if (id < 0 || id >= ns) continue;
         const float nx = s[3 * id] - qx, ny = s[3 * id + 1] - qy, nz = s[3 * id + 2] - qz;
-        const float w = kp_weight(nx, ny, nz, kp, k, inv_extent);
+        float w;
+        if constexpr (AGG == FGR_AGG_CLOSEST) {
+            // this thread owns one k: the argmin over all K is recomputed per neighbour
+            int bk;
+            w = kp_closest<INF>(nx, ny, nz, kp, n_kp, wscale, &bk);
+            w = bk == k ? w : 0.f;
+        } else {
+            w = kp_weight<INF>(nx, ny, nz, kp, k, wscale);
+        }
         const float* xr = x + id * cin;
         float rs = 0.f;
 #pragma unroll
@@ -331,11 +393,11 @@ kpconv_gather_narrow(const float* __restrict__ q, const float* __restrict__ s, i
 // reads), accumulates all K kernel-point sums, and the 16 lanes reduce them with DPP; lane
 // k then writes wf[q, k] (and k + 16), so each neighbour is read once per query instead of
 // once per (query, kernel point).
-template <int KU>
+template <int KU, int INF, int AGG>
 __global__ void __launch_bounds__(256)
 kpconv_gather_c1(const float* __restrict__ q, const float* __restrict__ s, int64_t nq, int64_t ns,
                  const int64_t* __restrict__ idx, int width, const float* __restrict__ x,
-                 const float* __restrict__ kp_g, int n_kp, float inv_extent,
+                 const float* __restrict__ kp_g, int n_kp, float wscale,
                  float* __restrict__ wf, float* __restrict__ nnorm) {
     __shared__ float kp[3 * kMaxKp];
     for (int i = threadIdx.x; i < 3 * n_kp; i += blockDim.x) kp[i] = kp_g[i];
@@ -355,9 +417,17 @@ kpconv_gather_c1(const float* __restrict__ q, const float* __restrict__ s, int64
         const float nx = s[3 * id] - qx, ny = s[3 * id + 1] - qy, nz = s[3 * id + 2] - qz;
         const float xv = x[id];
         n_pos += xv > 0.f ? 1.f : 0.f;
+        if constexpr (AGG == FGR_AGG_CLOSEST) {
+            // the unrolled k is a compile-time register index; only the comparison is run-time
+            int bk;
+            const float w = kp_closest<INF>(nx, ny, nz, kp, n_kp, wscale, &bk);
 #pragma unroll
-        for (int k = 0; k < KU; ++k)
-            if (k < n_kp) acc[k] = fmaf(kp_weight(nx, ny, nz, kp, k, inv_extent), xv, acc[k]);
+            for (int k = 0; k < KU; ++k) acc[k] = fmaf(k == bk ? w : 0.f, xv, acc[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < KU; ++k)
+                if (k < n_kp) acc[k] = fmaf(kp_weight<INF>(nx, ny, nz, kp, k, wscale), xv, acc[k]);
+        }
     }
     float mine0 = 0.f, mine1 = 0.f;
 #pragma unroll
@@ -375,27 +445,71 @@ kpconv_gather_c1(const float* __restrict__ q, const float* __restrict__ s, int64
     }
 }
 
-template <int CMAX>
-void launch_narrow(const float* q, const float* s, int64_t nq, int64_t ns, const int64_t* idx,
-                   int width, const float* x, int cin, const float* kp, int n_kp, float inv_ext,
-                   float* wf, float* nnorm, hipStream_t st) {
-    const int64_t n = nq * n_kp;
-    hipLaunchKernelGGL(kpconv_gather_narrow<CMAX>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0,
-                       st, q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm);
+struct GatherArgs {
+    const float* q; const float* s; int64_t nq, ns; const int64_t* idx; int width;
+    const float* x; int cin; const float* kp; int n_kp; float wscale; float* wf; float* nnorm;
+    hipStream_t st;
+};
+
+template <int CMAX, int INF, int AGG>
+void launch_narrow(const GatherArgs& a) {
+    const int64_t n = a.nq * a.n_kp;
+    hipLaunchKernelGGL((kpconv_gather_narrow<CMAX, INF, AGG>), dim3((unsigned)ceil_div(n, 256)),
+                       dim3(256), 0, a.st, a.q, a.s, a.nq, a.ns, a.idx, a.width, a.x, a.cin, a.kp,
+                       a.n_kp, a.wscale, a.wf, a.nnorm);
 }
 
-template <int VEC>
-void launch_wide_k(const float* q, const float* s, int64_t nq, int64_t ns, const int64_t* idx,
-                   int width, const float* x, const float* kp, int n_kp, float inv_ext, float* wf,
-                   float* nnorm, hipStream_t st) {
-    dim3 grid((unsigned)ceil_div(nq, kGatherWaves));
-    if (n_kp <= 16)
-        hipLaunchKernelGGL((kpconv_gather_wide<VEC, 16, true>), grid, dim3(64 * kGatherWaves), 0,
-                           st, q, s, nq, ns, idx, width, x, nullptr, kp, n_kp, inv_ext, wf, nnorm);
+template <int VEC, int INF, int AGG>
+void launch_wide_k(const GatherArgs& a) {
+    dim3 grid((unsigned)ceil_div(a.nq, kGatherWaves));
+    if (a.n_kp <= 16)
+        hipLaunchKernelGGL((kpconv_gather_wide<VEC, 16, true, INF, AGG>), grid,
+                           dim3(64 * kGatherWaves), 0, a.st, a.q, a.s, a.nq, a.ns, a.idx, a.width,
+                           a.x, nullptr, a.kp, a.n_kp, a.wscale, a.wf, a.nnorm);
     else
-        hipLaunchKernelGGL((kpconv_gather_wide<VEC, kMaxKp, true>), grid, dim3(64 * kGatherWaves),
-                           0, st, q, s, nq, ns, idx, width, x, nullptr, kp, n_kp, inv_ext, wf,
-                           nnorm);
+        hipLaunchKernelGGL((kpconv_gather_wide<VEC, kMaxKp, true, INF, AGG>), grid,
+                           dim3(64 * kGatherWaves), 0, a.st, a.q, a.s, a.nq, a.ns, a.idx, a.width,
+                           a.x, nullptr, a.kp, a.n_kp, a.wscale, a.wf, a.nnorm);
+}
+
+// The dispatch over widths, the same for every (INF, AGG). The wide kernel bakes
+// cin = 64 * VEC into its row strides and its vector accesses take VEC in {1, 2, 4}: every
+// other width (192 included) is refused by the caller, never rounded up
+template <int INF, int AGG>
+void launch_gather(const GatherArgs& a) {
+    const int cin = a.cin;
+    if (cin == 64) {
+        launch_wide_k<1, INF, AGG>(a);
+    } else if (cin == 128) {
+        launch_wide_k<2, INF, AGG>(a);
+    } else if (cin == 256) {
+        launch_wide_k<4, INF, AGG>(a);
+    } else if (cin == 1) {
+        const dim3 grid((unsigned)ceil_div(a.nq * 16, 256));
+        if (a.n_kp <= 16)
+            hipLaunchKernelGGL((kpconv_gather_c1<16, INF, AGG>), grid, dim3(256), 0, a.st, a.q, a.s,
+                               a.nq, a.ns, a.idx, a.width, a.x, a.kp, a.n_kp, a.wscale, a.wf,
+                               a.nnorm);
+        else
+            hipLaunchKernelGGL((kpconv_gather_c1<kMaxKp, INF, AGG>), grid, dim3(256), 0, a.st, a.q,
+                               a.s, a.nq, a.ns, a.idx, a.width, a.x, a.kp, a.n_kp, a.wscale, a.wf,
+                               a.nnorm);
+    } else if ((cin == 16 || cin == 32) && a.n_kp <= 16 &&
+               (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 &&
+               (reinterpret_cast<uintptr_t>(a.wf) & 15) == 0) {
+        const dim3 grid((unsigned)ceil_div(a.nq, 4));
+        if (cin == 32)
+            hipLaunchKernelGGL((kpconv_gather_quads<8, 2, INF, AGG>), grid, dim3(256), 0, a.st, a.q,
+                               a.s, a.nq, a.ns, a.idx, a.width, a.x, a.kp, a.n_kp, a.wscale, a.wf,
+                               a.nnorm);
+        else
+            hipLaunchKernelGGL((kpconv_gather_quads<4, 1, INF, AGG>), grid, dim3(256), 0, a.st, a.q,
+                               a.s, a.nq, a.ns, a.idx, a.width, a.x, a.kp, a.n_kp, a.wscale, a.wf,
+                               a.nnorm);
+    } else if (cin <= 8) launch_narrow<8, INF, AGG>(a);
+    else if (cin <= 16) launch_narrow<16, INF, AGG>(a);
+    else if (cin <= 32) launch_narrow<32, INF, AGG>(a);
+    else launch_narrow<64, INF, AGG>(a);
 }
 
 // max_pool, one wave per query (c % 64 == 0, VEC floats per lane): valid neighbours are
@@ -468,14 +582,19 @@ extern "C" int fgr_kpconv_gather_workspace(int64_t ns, int32_t cin, size_t* byte
     return FGR_OK;
 }
 
-extern "C" int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int64_t ns,
-                                 const int64_t* idx, int32_t width, const float* x, int32_t cin,
-                                 const float* kp, int32_t n_kp, float extent, float* wf,
-                                 float* nnorm, void* workspace, size_t ws_bytes, void* stream) {
+extern "C" int fgr_kpconv_gather_mode(const float* q, const float* s, int64_t nq, int64_t ns,
+                                      const int64_t* idx, int32_t width, const float* x,
+                                      int32_t cin, const float* kp, int32_t n_kp, float extent,
+                                      int32_t influence, int32_t aggregation, float* wf,
+                                      float* nnorm, void* workspace, size_t ws_bytes,
+                                      void* stream) {
     (void)workspace; (void)ws_bytes;
     FGR_REQUIRE(nq >= 0 && ns >= 0 && width >= 0 && cin > 0 && n_kp > 0 && n_kp <= kMaxKp &&
                     extent > 0.f,
                 "fgr_kpconv_gather: bad arguments (cin %d, n_kp %d, width %d)", cin, n_kp, width);
+    FGR_REQUIRE(kp_modes_ok(influence, aggregation),
+                "fgr_kpconv_gather_mode: unknown mode (influence %d, aggregation %d; need "
+                "FGR_KP_* 0..2 and FGR_AGG_* 0..1)", influence, aggregation);
     FGR_REQUIRE(nq == 0 || (q && s && x && kp && wf && nnorm && (idx || width == 0)),
                 "fgr_kpconv_gather: null pointer");
     FGR_REQUIRE(cin <= 64 || cin == 128 || cin == 256,
@@ -483,41 +602,22 @@ extern "C" int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int
     if (nq == 0) return FGR_OK;
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
-    const float inv_ext = 1.0f / extent;
-    // the wide kernel bakes cin = 64 * VEC into its row strides and its vector accesses take
-    // VEC in {1, 2, 4}: every other width (192 included) is refused below, never rounded up
-    if (cin == 64) {
-        launch_wide_k<1>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st);
-    } else if (cin == 128) {
-        launch_wide_k<2>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st);
-    } else if (cin == 256) {
-        launch_wide_k<4>(q, s, nq, ns, idx, width, x, kp, n_kp, inv_ext, wf, nnorm, st);
-    } else if (cin <= 64) {
-        if (cin == 1) {
-            const dim3 grid((unsigned)ceil_div(nq * 16, 256));
-            if (n_kp <= 16)
-                hipLaunchKernelGGL(kpconv_gather_c1<16>, grid, dim3(256), 0, st, q, s, nq, ns, idx,
-                                   width, x, kp, n_kp, inv_ext, wf, nnorm);
-            else
-                hipLaunchKernelGGL(kpconv_gather_c1<kMaxKp>, grid, dim3(256), 0, st, q, s, nq, ns,
-                                   idx, width, x, kp, n_kp, inv_ext, wf, nnorm);
-        } else if ((cin == 16 || cin == 32) && n_kp <= 16 &&
-                   (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(wf) & 15) == 0) {
-            const dim3 grid((unsigned)ceil_div(nq, 4));
-            if (cin == 32)
-                hipLaunchKernelGGL((kpconv_gather_quads<8, 2>), grid, dim3(256), 0, st, q, s, nq, ns,
-                                   idx, width, x, kp, n_kp, inv_ext, wf, nnorm);
-            else
-                hipLaunchKernelGGL((kpconv_gather_quads<4, 1>), grid, dim3(256), 0, st, q, s, nq, ns,
-                                   idx, width, x, kp, n_kp, inv_ext, wf, nnorm);
-        } else if (cin <= 8) launch_narrow<8>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
-        else if (cin <= 16) launch_narrow<16>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
-        else if (cin <= 32) launch_narrow<32>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
-        else launch_narrow<64>(q, s, nq, ns, idx, width, x, cin, kp, n_kp, inv_ext, wf, nnorm, st);
-    }
+    const GatherArgs a{q, s, nq, ns, idx, width, x, cin, kp, n_kp, kp_wscale(influence, extent),
+                       wf, nnorm, st};
+    kp_with_modes(influence, aggregation, [&](auto inf, auto agg) {
+        launch_gather<decltype(inf)::value, decltype(agg)::value>(a);
+    });
     FGR_CHECK_LAUNCH("kpconv_gather");
     return FGR_OK;
+}
+
+extern "C" int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int64_t ns,
+                                 const int64_t* idx, int32_t width, const float* x, int32_t cin,
+                                 const float* kp, int32_t n_kp, float extent, float* wf,
+                                 float* nnorm, void* workspace, size_t ws_bytes, void* stream) {
+    return fgr_kpconv_gather_mode(q, s, nq, ns, idx, width, x, cin, kp, n_kp, extent,
+                                  FGR_KP_LINEAR, FGR_AGG_SUM, wf, nnorm, workspace, ws_bytes,
+                                  stream);
 }
 
 extern "C" int fgr_max_pool(const float* x, int64_t ns, int32_t c, const int64_t* idx, int64_t nq,

@@ -124,11 +124,13 @@ csr_rowsum_kernel(const int* __restrict__ start, int64_t ns, const float* __rest
 // every 64-channel slice the query's dwf rows (K x 64) are held in registers and each valid
 // neighbour's contribution sum_k w_hk dwf[q, k, c] is written to its CSR slot of the inverse
 // (g[pos[q * width + h], c]); csr_rowsum_kernel then adds each support row's slots in order.
+// INF / AGG: the forward's influence function and aggregation mode (FGR_KP_*, FGR_AGG_*).
+template <int INF, int AGG>
 __global__ void __launch_bounds__(256)
 kpconv_scatter_rows_kernel(const float* __restrict__ q, const float* __restrict__ s, int64_t nq,
                            int64_t ns, const int64_t* __restrict__ idx, int width,
                            const float* __restrict__ dwf, int cin, const float* __restrict__ kp_g,
-                           int n_kp, float inv_extent, const int* __restrict__ pos,
+                           int n_kp, float wscale, const int* __restrict__ pos,
                            float* __restrict__ g) {
     __shared__ float w_lds[4][64][kMaxKpT + 1];
     __shared__ int slot_lds[4][64];
@@ -152,7 +154,14 @@ kpconv_scatter_rows_kernel(const float* __restrict__ q, const float* __restrict_
             const int p = __popcll(m & ((1ull << lane) - 1ull));
             slot_lds[wv][p] = pos[qi * width + h];
             const float nx = s[3 * id] - qx, ny = s[3 * id + 1] - qy, nz = s[3 * id + 2] - qz;
-            for (int k = 0; k < n_kp; ++k) w_lds[wv][p][k] = kp_weight(nx, ny, nz, kp, k, inv_extent);
+            if constexpr (AGG == FGR_AGG_CLOSEST) {
+                int bk;
+                const float wb = kp_closest<INF>(nx, ny, nz, kp, n_kp, wscale, &bk);
+                for (int k = 0; k < n_kp; ++k) w_lds[wv][p][k] = k == bk ? wb : 0.f;
+            } else {
+                for (int k = 0; k < n_kp; ++k)
+                    w_lds[wv][p][k] = kp_weight<INF>(nx, ny, nz, kp, k, wscale);
+            }
         }
         __builtin_amdgcn_wave_barrier();
         for (int c0 = 0; c0 < cin; c0 += 64) {
@@ -1245,13 +1254,17 @@ extern "C" int fgr_kpconv_scatter_workspace(int64_t nq, int32_t width, int32_t c
     return FGR_OK;
 }
 
-extern "C" int fgr_kpconv_scatter(const float* q, const float* s, int64_t nq, int64_t ns,
-                                  const int64_t* idx, int32_t width, const float* dwf, int32_t cin,
-                                  const float* kernel_points, int32_t n_kp, float extent,
-                                  const int32_t* start, const int32_t* pos, float* dx, void* ws,
-                                  size_t ws_bytes, void* stream) {
+extern "C" int fgr_kpconv_scatter_mode(const float* q, const float* s, int64_t nq, int64_t ns,
+                                       const int64_t* idx, int32_t width, const float* dwf,
+                                       int32_t cin, const float* kernel_points, int32_t n_kp,
+                                       float extent, int32_t influence, int32_t aggregation,
+                                       const int32_t* start, const int32_t* pos, float* dx,
+                                       void* ws, size_t ws_bytes, void* stream) {
     FGR_REQUIRE(nq >= 0 && ns >= 0 && width >= 0 && cin > 0 && n_kp > 0 && n_kp <= kMaxKpT &&
                     extent > 0.f, "fgr_kpconv_scatter: bad arguments");
+    FGR_REQUIRE(kp_modes_ok(influence, aggregation),
+                "fgr_kpconv_scatter_mode: unknown mode (influence %d, aggregation %d; need "
+                "FGR_KP_* 0..2 and FGR_AGG_* 0..1)", influence, aggregation);
     if (ns == 0) return FGR_OK;
     FGR_REQUIRE(start && dx && ws, "fgr_kpconv_scatter: null pointer");
     size_t need = 0;
@@ -1261,15 +1274,27 @@ extern "C" int fgr_kpconv_scatter(const float* q, const float* s, int64_t nq, in
     float* g = (float*)ws;
     if (nq > 0 && width > 0) {
         FGR_REQUIRE(q && s && idx && dwf && kernel_points && pos, "fgr_kpconv_scatter: null pointer");
-        hipLaunchKernelGGL(kpconv_scatter_rows_kernel, dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st,
-                           q, s, nq, ns, idx, width, dwf, cin, kernel_points, n_kp, 1.0f / extent,
-                           (const int*)pos, g);
+        const float wscale = kp_wscale(influence, extent);
+        kp_with_modes(influence, aggregation, [&](auto inf, auto agg) {
+            hipLaunchKernelGGL((kpconv_scatter_rows_kernel<decltype(inf)::value, decltype(agg)::value>),
+                               dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st, q, s, nq, ns, idx,
+                               width, dwf, cin, kernel_points, n_kp, wscale, (const int*)pos, g);
+        });
         FGR_CHECK_LAUNCH("kpconv_scatter_rows_kernel");
     }
     hipLaunchKernelGGL(csr_rowsum_kernel, dim3((unsigned)ceil_div(ns * cin, 256)), dim3(256), 0, st,
                        (const int*)start, ns, (const float*)g, cin, dx);
     FGR_CHECK_LAUNCH("csr_rowsum_kernel");
     return FGR_OK;
+}
+
+extern "C" int fgr_kpconv_scatter(const float* q, const float* s, int64_t nq, int64_t ns,
+                                  const int64_t* idx, int32_t width, const float* dwf, int32_t cin,
+                                  const float* kernel_points, int32_t n_kp, float extent,
+                                  const int32_t* start, const int32_t* pos, float* dx, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    return fgr_kpconv_scatter_mode(q, s, nq, ns, idx, width, dwf, cin, kernel_points, n_kp, extent,
+                                   FGR_KP_LINEAR, FGR_AGG_SUM, start, pos, dx, ws, ws_bytes, stream);
 }
 
 extern "C" int fgr_max_pool_bwd_workspace(int64_t nq, int32_t c, size_t* bytes) {

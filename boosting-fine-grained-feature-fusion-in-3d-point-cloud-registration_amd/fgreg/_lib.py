@@ -34,6 +34,8 @@ SIGNATURES = {
     'fgr_kpconv_gather_workspace': [_i64, _i32, ctypes.POINTER(_sz)],
     'fgr_kpconv_gather': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp,
                           _vp, _sz, _vp],
+    'fgr_kpconv_gather_mode': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _i32,
+                               _i32, _vp, _vp, _vp, _sz, _vp],
     'fgr_max_pool': [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp],
     'fgr_instnorm_workspace': [_i64, _i32, _i32, ctypes.POINTER(_sz)],
     'fgr_instnorm': [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _f32, _i32, _vp, _i32, _vp, _vp, _sz,
@@ -131,6 +133,8 @@ SIGNATURES = {
     'fgr_kpconv_scatter_workspace': [_i64, _i32, _i32, ctypes.POINTER(_sz)],
     'fgr_kpconv_scatter': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp,
                            _vp, _vp, _sz, _vp],
+    'fgr_kpconv_scatter_mode': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _i32,
+                                _i32, _vp, _vp, _vp, _vp, _sz, _vp],
     'fgr_max_pool_bwd_workspace': [_i64, _i32, ctypes.POINTER(_sz)],
     'fgr_max_pool_bwd': [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'fgr_corr_attention_bwd_workspace': [_i64, ctypes.POINTER(_sz)],

@@ -175,9 +175,11 @@ def nbr_inverse(idx: torch.Tensor, ns: int):
     return res
 
 
-def kpconv_scatter(q, s, idx, dwf, kp, extent):
-    """dx (ns, cin) of the KPConv gather from d_wf (nq, K * cin): fgr_kpconv_scatter over the
-    table's inverse (deterministic: each support row adds its entries in CSR order)."""
+def kpconv_scatter(q, s, idx, dwf, kp, extent, influence='linear', aggregation='sum'):
+    """dx (ns, cin) of the KPConv gather from d_wf (nq, K * cin): fgr_kpconv_scatter_mode over the
+    table's inverse (deterministic: each support row adds its entries in CSR order), with the
+    forward's influence function and aggregation mode (ops.kpconv_gather)."""
+    inf, agg = ops.kp_modes(influence, aggregation)
     _dev(q, s, idx, dwf, kp)
     nq, width = idx.shape
     ns = s.shape[0]
@@ -188,20 +190,21 @@ def kpconv_scatter(q, s, idx, dwf, kp, extent):
     L = _lib.load()
     nb = _lib.ws_size('fgr_kpconv_scatter_workspace', nq, width, cin)
     ws = ops._workspace(dwf.device, nb)         # grow-only scratch, not a fresh buffer per call
-    _lib.check(L.fgr_kpconv_scatter(
+    _lib.check(L.fgr_kpconv_scatter_mode(
         _ptr(_c(q, torch.float32)), _ptr(_c(s, torch.float32)), nq, ns, _ptr(_c(idx, torch.int64)),
-        width, _ptr(dwf), cin, _ptr(_c(kp, torch.float32)), K, float(extent), _ptr(start),
-        _ptr(pos), _ptr(dx), _ptr(ws), nb, _stream()), 'fgr_kpconv_scatter')
+        width, _ptr(dwf), cin, _ptr(_c(kp, torch.float32)), K, float(extent), inf, agg,
+        _ptr(start), _ptr(pos), _ptr(dx), _ptr(ws), nb, _stream()), 'fgr_kpconv_scatter_mode')
     return dx
 
 
 class _KPConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, W, q, s, idx, kp, extent):
-        wf, nnorm = ops.kpconv_gather(q, s, idx, x, kp, extent)
+    def forward(ctx, x, W, q, s, idx, kp, extent, influence='linear', aggregation='sum'):
+        wf, nnorm = ops.kpconv_gather(q, s, idx, x, kp, extent, influence, aggregation)
         out = linear(wf.view(wf.shape[0], -1), W, transpose=True)
         ctx.mode = lin.MODE
         ctx.extent = float(extent)
+        ctx.kp_modes = (influence, aggregation)
         ctx.save_for_backward(x, W, q, s, idx, kp)
         ctx.mark_non_differentiable(nnorm)
         return out, nnorm
@@ -216,17 +219,21 @@ class _KPConvFn(torch.autograd.Function):
         with lin.mode_scope(ctx.mode):
             if ctx.needs_input_grad[0]:
                 dwf = linear(dout, W, transpose='flat', tag='bwd_dwf')       # (nq, K * cin)
-                dx = kpconv_scatter(q, s, idx, dwf, kp, ctx.extent)
+                dx = kpconv_scatter(q, s, idx, dwf, kp, ctx.extent, *ctx.kp_modes)
             if ctx.needs_input_grad[1]:
-                wf, _ = ops.kpconv_gather(q, s, idx, x, kp, ctx.extent)      # regathered
+                wf, _ = ops.kpconv_gather(q, s, idx, x, kp, ctx.extent, *ctx.kp_modes)   # regathered
                 dW = wgrad(wf.view(nq, K * cin), dout).view(K, cin, cout)   # wf^T dout
-        return dx, dW, None, None, None, None, None
+        return dx, dW, None, None, None, None, None, None, None
 
 
 def kpconv_t(conv, q, s, idx, x):
     """-> (sum_k WF_k W_k (Nq, Cout), nnorm (Nq,)) of a fgreg.backbone.KPConv, differentiable in
-    x and the weights (kernel points are fixed, as requires_grad=False in the reference)."""
-    return _KPConvFn.apply(x, conv.weights, q, s, idx, conv.kernel_points, conv.KP_extent)
+    x and the weights (kernel points are fixed, as requires_grad=False in the reference). The
+    influence function and aggregation mode are the conv's KP_influence / aggregation_mode
+    (linear / sum for an object without them)."""
+    return _KPConvFn.apply(x, conv.weights, q, s, idx, conv.kernel_points, conv.KP_extent,
+                           getattr(conv, 'KP_influence', 'linear'),
+                           getattr(conv, 'aggregation_mode', 'sum'))
 
 
 class _MaxPoolFn(torch.autograd.Function):

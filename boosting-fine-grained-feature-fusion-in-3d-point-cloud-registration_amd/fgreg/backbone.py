@@ -189,14 +189,20 @@ def init_kernel_points(radius, n_kp, rng=np.random):
 # Blocks
 # ------------------------------------------------------------------------------------------
 class KPConv(nn.Module):
-    """Rigid KPConv (finegrained_kpconv_blocks.py:171-401): linear influence, sum mode."""
+    """Rigid KPConv (finegrained_kpconv_blocks.py:171-401) with the reference's influence
+    functions (KP_influence: linear | gaussian | constant) and aggregation modes
+    (aggregation_mode: sum | closest). An unknown value raises ValueError with the reference's
+    message here, at construction; the reference raises it at the first forward (:364, :372).
+    Deformable / modulated KPConv and p_dim != 3 are not implemented."""
 
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius,
                  fixed_kernel_points='center', KP_influence='linear', aggregation_mode='sum',
                  deformable=False, modulated=False):
         super().__init__()
-        if deformable or KP_influence != 'linear' or aggregation_mode != 'sum' or p_dim != 3:
-            raise NotImplementedError('only the rigid/linear/sum KPConv of the reference configs')
+        if deformable or p_dim != 3:
+            raise NotImplementedError('only the rigid 3-D KPConv of the reference configs')
+        ops.kp_modes(KP_influence, aggregation_mode)          # ValueError for an unknown value
+        self.KP_influence, self.aggregation_mode = KP_influence, aggregation_mode
         self.K, self.p_dim = kernel_size, p_dim
         self.in_channels, self.out_channels = in_channels, out_channels
         self.radius, self.KP_extent = radius, KP_extent
@@ -209,7 +215,7 @@ class KPConv(nn.Module):
         """-> (sum_k WF_k @ W_k (Nq, Cout), nnorm (Nq,)). The reference divides the first
         by the second (:395-399); callers fuse that division into the next kernel."""
         wf, nnorm = ops.kpconv_gather(q_pts, s_pts, neighb_inds, x, self.kernel_points,
-                                      self.KP_extent)
+                                      self.KP_extent, self.KP_influence, self.aggregation_mode)
         out = linear(wf.view(wf.shape[0], -1), self.weights, transpose=True)
         return out, nnorm
 

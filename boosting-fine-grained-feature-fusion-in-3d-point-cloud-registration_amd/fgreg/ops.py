@@ -375,8 +375,27 @@ def radius_search(q: torch.Tensor, q_off: torch.Tensor, q_lengths: Sequence[int]
 # ------------------------------------------------------------------------------------------
 # KPConv
 # ------------------------------------------------------------------------------------------
-def kpconv_gather(q, s, idx, x, kernel_points, extent) -> Tuple[torch.Tensor, torch.Tensor]:
-    """-> (wf (Nq, K, Cin), nnorm (Nq,) f32) of the KPConv gather-weight stage."""
+KP_INFLUENCES = {'linear': 0, 'gaussian': 1, 'constant': 2}       # FGR_KP_* of include/fgreg.h
+KP_AGGREGATIONS = {'sum': 0, 'closest': 1}                        # FGR_AGG_*
+
+
+def kp_modes(influence, aggregation) -> Tuple[int, int]:
+    """The FGR_KP_* / FGR_AGG_* codes of a config's KP_influence and aggregation_mode; an unknown
+    value raises ValueError with the reference's message (finegrained_kpconv_blocks.py:364,
+    :372)."""
+    if influence not in KP_INFLUENCES:
+        raise ValueError('Unknown influence function type (config.KP_influence)')
+    if aggregation not in KP_AGGREGATIONS:
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    return KP_INFLUENCES[influence], KP_AGGREGATIONS[aggregation]
+
+
+def kpconv_gather(q, s, idx, x, kernel_points, extent, influence='linear',
+                  aggregation='sum') -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (wf (Nq, K, Cin), nnorm (Nq,) f32) of the KPConv gather-weight stage, with the
+    influence function ('linear' | 'gaussian' | 'constant') and aggregation mode ('sum' |
+    'closest') of blocks:347-372. fp32 in every precision mode."""
+    inf, agg = kp_modes(influence, aggregation)
     _dev(q, s, idx, x, kernel_points)
     q, s, x = _c(q, torch.float32), _c(s, torch.float32), _c(x, torch.float32)
     idx = _c(idx, torch.int64)
@@ -392,9 +411,10 @@ def kpconv_gather(q, s, idx, x, kernel_points, extent) -> Tuple[torch.Tensor, to
     _lib.check(L.fgr_kpconv_gather_workspace(ns, cin, nb), 'fgr_kpconv_gather_workspace')
     ws = _workspace(q.device, nb.value) if nb.value else None
     t0 = _begin('kpconv_gather', (nq, idx.shape[1], cin, K))
-    _lib.check(L.fgr_kpconv_gather(_ptr(q), _ptr(s), nq, ns, _ptr(idx), idx.shape[1], _ptr(x), cin,
-                                   _ptr(kp), K, float(extent), _ptr(wf), _ptr(nnorm), _ptr(ws),
-                                   nb.value, _stream()), 'fgr_kpconv_gather')
+    _lib.check(L.fgr_kpconv_gather_mode(_ptr(q), _ptr(s), nq, ns, _ptr(idx), idx.shape[1], _ptr(x),
+                                        cin, _ptr(kp), K, float(extent), inf, agg, _ptr(wf),
+                                        _ptr(nnorm), _ptr(ws), nb.value, _stream()),
+               'fgr_kpconv_gather_mode')
     _end('kpconv_gather', t0, lambda: gather_bytes(idx, ns, cin, K))
     return wf, nnorm
 

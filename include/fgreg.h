@@ -137,6 +137,27 @@ int fgr_kpconv_gather(const float* q, const float* s, int64_t nq, int64_t ns, co
                       float extent, float* wf, float* nnorm, void* workspace, size_t ws_bytes,
                       void* stream);
 
+/* The other influence functions and aggregation modes of KPConv.forward (:347-372). With
+ * d2 = |(s[idx[q,h]] - q) - kp[k]|^2 the weight of neighbour h at kernel point k is
+ *   FGR_KP_LINEAR    max(0, 1 - sqrt(d2) / extent)                      (fgr_kpconv_gather)
+ *   FGR_KP_GAUSSIAN  exp(-d2 / (2 (0.3 extent)^2 + 1e-9))               (radius_gaussian, :100-107)
+ *   FGR_KP_CONSTANT  1
+ * and FGR_AGG_CLOSEST multiplies it by [k == argmin_k d2] (the lowest k on an exact tie).
+ * Shadow entries are skipped in every mode (their feature row is zero in the reference) and
+ * nnorm does not depend on the mode. fgr_kpconv_gather_mode takes the arguments, widths,
+ * workspace and refusals of fgr_kpconv_gather, which is its (FGR_KP_LINEAR, FGR_AGG_SUM)
+ * case; any other mode value returns FGR_E_ARG before anything is launched or written. */
+#define FGR_KP_LINEAR 0
+#define FGR_KP_GAUSSIAN 1
+#define FGR_KP_CONSTANT 2
+#define FGR_AGG_SUM 0
+#define FGR_AGG_CLOSEST 1
+int fgr_kpconv_gather_mode(const float* q, const float* s, int64_t nq, int64_t ns,
+                           const int64_t* idx, int32_t width, const float* x, int32_t cin,
+                           const float* kp, int32_t n_kp, float extent, int32_t influence,
+                           int32_t aggregation, float* wf, float* nnorm, void* workspace,
+                           size_t ws_bytes, void* stream);
+
 /* max_pool (finegrained_kpconv_blocks.py:125-141): out[q, c] = max over the row of
  * x[idx[q, h], c], shadow entries contributing 0 (the appended zero row). */
 int fgr_max_pool(const float* x, int64_t ns, int32_t c, const int64_t* idx, int64_t nq,
@@ -683,6 +704,14 @@ int fgr_kpconv_scatter(const float* q, const float* s, int64_t nq, int64_t ns, c
                        int32_t width, const float* dwf, int32_t cin, const float* kernel_points,
                        int32_t n_kp, float extent, const int32_t* start, const int32_t* pos,
                        float* dx, void* ws, size_t ws_bytes, void* stream);
+/* fgr_kpconv_scatter with the influences of fgr_kpconv_gather_mode (FGR_KP_*, FGR_AGG_*): the
+ * same arguments, workspace and refusals; fgr_kpconv_scatter is its (0, 0) case */
+int fgr_kpconv_scatter_mode(const float* q, const float* s, int64_t nq, int64_t ns,
+                            const int64_t* idx, int32_t width, const float* dwf, int32_t cin,
+                            const float* kernel_points, int32_t n_kp, float extent,
+                            int32_t influence, int32_t aggregation, const int32_t* start,
+                            const int32_t* pos, float* dx, void* ws, size_t ws_bytes,
+                            void* stream);
 int fgr_max_pool_bwd_workspace(int64_t nq, int32_t c, size_t* bytes);
 int fgr_max_pool_bwd(const float* x, int64_t ns, int32_t c, const int64_t* idx, int64_t nq,
                      int32_t width, const float* dy, const int32_t* start, const int32_t* ent,

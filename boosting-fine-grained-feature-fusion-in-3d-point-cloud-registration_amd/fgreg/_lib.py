@@ -36,6 +36,15 @@ SIGNATURES = {
                           _vp, _sz, _vp],
     'fgr_kpconv_gather_mode': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _i32,
                                _i32, _vp, _vp, _vp, _sz, _vp],
+    'fgr_kpconv_deform_points': [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp],
+    'fgr_kpconv_gather_deform_workspace': [_i64, _i32, ctypes.POINTER(_sz)],
+    'fgr_kpconv_gather_deform': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32,
+                                 _i32, _i32, _vp, _vp, _vp, _sz, _vp],
+    'fgr_kpconv_scatter_deform_workspace': [_i64, _i32, _i32, ctypes.POINTER(_sz)],
+    'fgr_kpconv_scatter_deform': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32,
+                                  _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp],
+    'fgr_kpconv_deform_grad': [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32,
+                               _f32, _i32, _i32, _vp, _vp, _vp],
     'fgr_max_pool': [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp],
     'fgr_instnorm_workspace': [_i64, _i32, _i32, ctypes.POINTER(_sz)],
     'fgr_instnorm': [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _f32, _i32, _vp, _i32, _vp, _vp, _sz,

@@ -12,6 +12,10 @@ Each op is a ``torch.autograd.Function`` whose forward AND backward run in libfg
                     d_wf = dout W2^T (GEMM), dW = wf^T dout (GEMM; wf regathered, not kept),
                     dx = fgr_kpconv_scatter(d_wf) (the scatter-add of the reference's
                     ``gather(method=2)``, :66-97, as a gather over the table's inverse);
+* ``kpconv_deform_t`` the deformable / modulated KPConv (:270-345, :384-385): the offset conv is
+                    a kpconv_t, the gather under per-query kernel points has dx =
+                    fgr_kpconv_scatter_deform, d kernel points / d modulations =
+                    fgr_kpconv_deform_grad (one owner per (query, kernel point): no atomics);
 * ``segnorm_t``     per-(segment, channel) normalisation with batch statistics
                     (fgr_segnorm_*): InstanceNorm per cloud (BatchNormBlock, :462-518) and the
                     Res2Net BatchNorm1d in train() (res2net.py:126-159, one segment + affine,
@@ -234,6 +238,112 @@ def kpconv_t(conv, q, s, idx, x):
     return _KPConvFn.apply(x, conv.weights, q, s, idx, conv.kernel_points, conv.KP_extent,
                            getattr(conv, 'KP_influence', 'linear'),
                            getattr(conv, 'aggregation_mode', 'sum'))
+
+
+def kpconv_scatter_deform(q, s, idx, dwf, kp_q, mod, extent, influence='linear', aggregation='sum'):
+    """dx (ns, cin) of the deformable gather from d_wf (nq, K * cin): fgr_kpconv_scatter_deform
+    over the table's inverse, as kpconv_scatter, under the forward's kp_q / mod."""
+    inf, agg = ops.kp_modes(influence, aggregation)
+    _dev(q, s, idx, dwf, kp_q, mod)
+    nq, width = idx.shape
+    ns, K = s.shape[0], kp_q.shape[1]
+    cin = dwf.shape[1] // K
+    start, pos, _ = nbr_inverse(idx, ns)
+    dx = torch.empty((ns, cin), dtype=torch.float32, device=dwf.device)
+    nb = _lib.ws_size('fgr_kpconv_scatter_deform_workspace', nq, width, cin)
+    ws = ops._workspace(dwf.device, nb)
+    _lib.check(_lib.load().fgr_kpconv_scatter_deform(
+        _ptr(_c(q, torch.float32)), _ptr(_c(s, torch.float32)), nq, ns, _ptr(_c(idx, torch.int64)),
+        width, _ptr(dwf), cin, _ptr(kp_q), _ptr(mod), K, float(extent), inf, agg, _ptr(start),
+        _ptr(pos), _ptr(dx), _ptr(ws), nb, _stream()), 'fgr_kpconv_scatter_deform')
+    return dx
+
+
+def kpconv_deform_grad(q, s, idx, x, dwf, kp_q, mod, extent, influence='linear', aggregation='sum'):
+    """-> (d_kp (nq, K, 3), d_mod (nq, K) or None) of the deformable gather from d_wf
+    (fgr_kpconv_deform_grad: one wave per query, no atomics)."""
+    inf, agg = ops.kp_modes(influence, aggregation)
+    _dev(q, s, idx, x, dwf, kp_q, mod)
+    nq, width = idx.shape
+    ns, K, cin = s.shape[0], kp_q.shape[1], x.shape[1]
+    d_kp = torch.empty_like(kp_q)
+    d_mod = None if mod is None else torch.empty_like(mod)
+    _lib.check(_lib.load().fgr_kpconv_deform_grad(
+        _ptr(_c(q, torch.float32)), _ptr(_c(s, torch.float32)), nq, ns, _ptr(_c(idx, torch.int64)),
+        width, _ptr(x), cin, _ptr(dwf), _ptr(kp_q), _ptr(mod), K, float(extent), inf, agg,
+        _ptr(d_kp), _ptr(d_mod), _stream()), 'fgr_kpconv_deform_grad')
+    return d_kp, d_mod
+
+
+class _KPConvDeformFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, W, kp_q, mod, q, s, idx, extent, influence='linear', aggregation='sum'):
+        x, kp_q = _c(x, torch.float32), _c(kp_q, torch.float32)
+        mod = None if mod is None else _c(mod, torch.float32)
+        wf, nnorm = ops.kpconv_gather_deform(q, s, idx, x, kp_q, mod, extent, influence, aggregation)
+        out = linear(wf.view(wf.shape[0], -1), W, transpose=True)
+        ctx.mode = lin.MODE
+        ctx.extent = float(extent)
+        ctx.kp_modes = (influence, aggregation)
+        ctx.has_mod = mod is not None
+        ctx.save_for_backward(x, W, kp_q, mod, q, s, idx)
+        ctx.mark_non_differentiable(nnorm)
+        return out, nnorm
+
+    @staticmethod
+    def backward(ctx, dout, _dnnorm):
+        x, W, kp_q, mod, q, s, idx = ctx.saved_tensors
+        dout = dout.contiguous()
+        nq = q.shape[0]
+        K, cin, cout = W.shape
+        dx = dW = d_kp = d_mod = None
+        need = ctx.needs_input_grad
+        with lin.mode_scope(ctx.mode):
+            if need[0] or need[2] or (ctx.has_mod and need[3]):
+                dwf = linear(dout, W, transpose='flat', tag='bwd_dwf')       # (nq, K * cin)
+                if need[0]:
+                    dx = kpconv_scatter_deform(q, s, idx, dwf, kp_q, mod, ctx.extent, *ctx.kp_modes)
+                if need[2] or (ctx.has_mod and need[3]):
+                    d_kp, d_mod = kpconv_deform_grad(q, s, idx, x, dwf, kp_q, mod, ctx.extent,
+                                                     *ctx.kp_modes)
+            if need[1]:
+                wf, _ = ops.kpconv_gather_deform(q, s, idx, x, kp_q, mod, ctx.extent,
+                                                 *ctx.kp_modes)                # regathered
+                dW = wgrad(wf.view(nq, K * cin), dout).view(K, cin, cout)   # wf^T dout
+        return dx, dW, d_kp, d_mod, None, None, None, None, None, None
+
+
+def kpconv_deform_gather_t(x, W, kp_q, mod, q, s, idx, extent, influence='linear',
+                           aggregation='sum'):
+    """-> (sum_k WF_k W_k, nnorm) of the deformable gather under given kernel points kp_q
+    (Nq, K, 3) and modulations mod (Nq, K) or None, differentiable in x, W, kp_q and mod."""
+    return _KPConvDeformFn.apply(x, W, kp_q, mod, q, s, idx, extent, influence, aggregation)
+
+
+def deform_points_t(conv, raw, rn):
+    """The elementwise chain of blocks:272-306 in torch ops (differentiable): the offset conv's
+    raw product and normaliser -> (kp_q (nq, K, 3), mod (nq, K) or None)."""
+    f = raw / rn.unsqueeze(1) + conv.offset_bias
+    K = conv.K
+    kp_q = conv.kernel_points + (f[:, :3 * K] * conv.KP_extent).view(-1, K, 3)
+    mod = 2 * torch.sigmoid(f[:, 3 * K:]) if conv.modulated else None
+    return kp_q, mod
+
+
+def kpconv_deform_t(conv, q, s, idx, x):
+    """-> (sum_k WF_k W_k (Nq, Cout), nnorm (Nq,)) of a fgreg.backbone.DeformableKPConv,
+    differentiable in x, the weights, offset_bias and the offset conv's weights: the offset conv
+    is a kpconv_t (its weight product in the f16x3 mode in every precision mode, as in the
+    inference forward), the offsets -> kernel points / modulations chain is torch, and one
+    autograd function holds fgr_kpconv_gather_deform, the weight GEMM and their backward
+    (fgr_kpconv_scatter_deform, fgr_kpconv_deform_grad, wgrad on the regathered wf). The
+    in-range mask and the closest one-hot are constants of the backward."""
+    with lin.mode_scope('f16x3'):
+        raw, rn = kpconv_t(conv.offset_conv, q, s, idx, x)
+    kp_q, mod = deform_points_t(conv, raw, rn)
+    conv.deformed_KP, conv._offset_raw = kp_q.detach(), (raw.detach(), rn)
+    return kpconv_deform_gather_t(x, conv.weights, kp_q, mod, q, s, idx, conv.KP_extent,
+                                  conv.KP_influence, conv.aggregation_mode)
 
 
 class _MaxPoolFn(torch.autograd.Function):

@@ -10,6 +10,8 @@ The compute path is:
 * ``KPConv``            -- fgr_kpconv_gather (HBM-bound gather-weight) + one
   (Nq, K*Cin) x (K*Cin, Cout) GEMM; the 1/nnorm normaliser is folded into the
   following instance norm;
+* ``DeformableKPConv``  -- a rigid offset KPConv -> fgr_kpconv_deform_points (per-query kernel
+  points and modulations) -> fgr_kpconv_gather_deform (in-range neighbours only) + the GEMM;
 * ``BatchNormBlock``    -- fgr_instnorm (per-cloud InstanceNorm1d, fused act/residual);
 * ``my_res2Net``        -- BatchNorm folded into the Linear weights (eval) + GEMMs.
 
@@ -27,6 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import linear as lin
 from . import ops
 from .linear import linear
 
@@ -88,11 +91,13 @@ class PreprocessorHIP(nn.Module):
                 layer_blocks.append(block)
                 if bi < len(arch) - 1 and 'upsample' not in arch[bi + 1]:
                     continue
-            if any('deformable' in b for b in layer_blocks[:-1]) or 'deformable' in block:
-                raise NotImplementedError('deformable KPConv is not used by the reference configs')
-            r = r_normal
-            # one cell grid over this level's points serves the conv and the pool tables
-            # (same supports, same radius); None for small clouds (brute-force scan)
+            # deformable layers search a wider ball (:472-475, :498-509): the conv table iff a
+            # block of the level other than its last is deformable (the reference's own
+            # layer_blocks[:-1]), the pool table iff the strided block is
+            r_deform = r_normal * cfg.deform_radius / cfg.conv_radius
+            r = r_deform if any('deformable' in b for b in layer_blocks[:-1]) else r_normal
+            # one cell grid over this level's points serves the conv and the pool tables where
+            # their radii are equal (same supports); None for small clouds (brute-force scan)
             grid = ops.radius_grid(points, off, lens, r)
             if layer_blocks:
                 conv_i = ops.radius_search(points, off, lens, points, off, lens, r, limits[layer],
@@ -103,6 +108,10 @@ class PreprocessorHIP(nn.Module):
                 dl = 2 * r_normal / cfg.conv_radius
                 pool_p, pool_lens, pool_len_dev, pool_off = ops.grid_subsample(points, off, lens, dl,
                                                                                device_layout=True)
+                r_pool = r_deform if 'deformable' in block else r_normal
+                if r_pool != r:
+                    r = r_pool
+                    grid = ops.radius_grid(points, off, lens, r)
                 pool_i = ops.radius_search(pool_p, pool_off, pool_lens, points, off, lens, r,
                                            limits[layer], self.mode, grid=grid)
                 up_grid = ops.radius_grid(pool_p, pool_off, pool_lens, 2 * r)
@@ -193,14 +202,17 @@ class KPConv(nn.Module):
     functions (KP_influence: linear | gaussian | constant) and aggregation modes
     (aggregation_mode: sum | closest). An unknown value raises ValueError with the reference's
     message here, at construction; the reference raises it at the first forward (:364, :372).
-    Deformable / modulated KPConv and p_dim != 3 are not implemented."""
+    The deformable / modulated KPConv is DeformableKPConv; p_dim != 3 is not implemented."""
 
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius,
                  fixed_kernel_points='center', KP_influence='linear', aggregation_mode='sum',
                  deformable=False, modulated=False):
         super().__init__()
-        if deformable or p_dim != 3:
-            raise NotImplementedError('only the rigid 3-D KPConv of the reference configs')
+        if deformable:
+            raise NotImplementedError('KPConv is the rigid convolution: build a DeformableKPConv '
+                                      'for deformable=True')
+        if p_dim != 3:
+            raise NotImplementedError('only the 3-D KPConv of the reference configs')
         ops.kp_modes(KP_influence, aggregation_mode)          # ValueError for an unknown value
         self.KP_influence, self.aggregation_mode = KP_influence, aggregation_mode
         self.K, self.p_dim = kernel_size, p_dim
@@ -222,6 +234,88 @@ class KPConv(nn.Module):
     def forward(self, q_pts, s_pts, neighb_inds, x):
         out, nnorm = self.forward_unnormalized(q_pts, s_pts, neighb_inds, x)
         return out / nnorm.unsqueeze(1)
+
+
+class DeformableKPConv(nn.Module):
+    """KPConv(deformable=True) of the reference (finegrained_kpconv_blocks.py:215-234, :270-345,
+    :384-385), its parameter names included: ``weights``, ``kernel_points``, ``offset_bias`` and
+    the rigid ``offset_conv`` (in_channels -> 3K offsets, 4K with ``modulated``: K modulations).
+
+    forward: offset features = offset_conv(x) + offset_bias; every query's kernel points move by
+    extent * offsets; a neighbour out of every deformed kernel point's range counts as a shadow
+    (the reference's topk re-indexing, here inside fgr_kpconv_gather_deform: no host readback, so
+    the forward stays graph-capturable); modulations scale the weighted features. The offset
+    conv's weight product runs in the fp32-accurate f16x3 mode in every precision mode: a bf16
+    offset would move neighbours across the in-range boundary. After a forward ``deformed_KP``
+    (Nq, K, 3) and ``offset_features`` hold that call's values; ``min_d2`` is not provided (this
+    reference has no regulariser loss that would read it)."""
+
+    def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius,
+                 fixed_kernel_points='center', KP_influence='linear', aggregation_mode='sum',
+                 modulated=False):
+        super().__init__()
+        if p_dim != 3:
+            raise NotImplementedError('only the 3-D KPConv of the reference configs')
+        ops.kp_modes(KP_influence, aggregation_mode)          # ValueError for an unknown value
+        self.KP_influence, self.aggregation_mode = KP_influence, aggregation_mode
+        self.K, self.p_dim = kernel_size, p_dim
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.radius, self.KP_extent = radius, KP_extent
+        self.deformable, self.modulated = True, bool(modulated)
+        self.offset_dim = (p_dim + 1 if modulated else p_dim) * kernel_size
+        # registration order = the reference's state_dict order
+        self.weights = nn.Parameter(torch.zeros((kernel_size, in_channels, out_channels)))
+        self.offset_conv = KPConv(kernel_size, p_dim, in_channels, self.offset_dim, KP_extent,
+                                  radius, fixed_kernel_points=fixed_kernel_points,
+                                  KP_influence=KP_influence, aggregation_mode=aggregation_mode)
+        self.offset_bias = nn.Parameter(torch.zeros(self.offset_dim))
+        nn.init.kaiming_uniform_(self.weights, a=math.sqrt(5))
+        self.kernel_points = nn.Parameter(
+            torch.tensor(init_kernel_points(radius, kernel_size)), requires_grad=False)
+        self.deformed_KP = None
+        self._offset_raw = None
+
+    @property
+    def offset_features(self):
+        """offset_conv(x) + offset_bias of the last forward (:272), or None before one."""
+        if self._offset_raw is None:
+            return None
+        raw, rn = self._offset_raw
+        return raw / rn.unsqueeze(1) + self.offset_bias
+
+    def deform(self, q_pts, s_pts, neighb_inds, x):
+        """-> (kp_q (Nq, K, 3), mod (Nq, K) or None) of this input."""
+        with lin.mode_scope('f16x3'):
+            raw, rn = self.offset_conv.forward_unnormalized(q_pts, s_pts, neighb_inds, x)
+        self._offset_raw = (raw, rn)
+        return ops.kpconv_deform_points(raw, rn, self.offset_bias, self.kernel_points,
+                                        self.KP_extent, self.modulated)
+
+    def forward_unnormalized(self, q_pts, s_pts, neighb_inds, x):
+        """-> (sum_k WF_k @ W_k (Nq, Cout), nnorm (Nq,)), as KPConv.forward_unnormalized; nnorm
+        counts the in-range neighbours only."""
+        kp_q, mod = self.deform(q_pts, s_pts, neighb_inds, x)
+        self.deformed_KP = kp_q
+        wf, nnorm = ops.kpconv_gather_deform(q_pts, s_pts, neighb_inds, x, kp_q, mod,
+                                             self.KP_extent, self.KP_influence,
+                                             self.aggregation_mode)
+        out = linear(wf.view(wf.shape[0], -1), self.weights, transpose=True)
+        return out, nnorm
+
+    def forward(self, q_pts, s_pts, neighb_inds, x):
+        out, nnorm = self.forward_unnormalized(q_pts, s_pts, neighb_inds, x)
+        return out / nnorm.unsqueeze(1)
+
+
+def make_kpconv(block_name, config, in_dim, out_dim, extent, radius):
+    """The KPConv of a block: deformable iff the block's name says so (blocks:611, :675)."""
+    kw = dict(fixed_kernel_points=config.fixed_kernel_points, KP_influence=config.KP_influence,
+              aggregation_mode=config.aggregation_mode)
+    if 'deform' in block_name:
+        return DeformableKPConv(config.num_kernel_points, config.in_points_dim, in_dim, out_dim,
+                                extent, radius, modulated=config.modulated, **kw)
+    return KPConv(config.num_kernel_points, config.in_points_dim, in_dim, out_dim, extent, radius,
+                  modulated=config.modulated, **kw)
 
 
 class BatchNormBlock(nn.Module):
@@ -380,11 +474,7 @@ class SimpleBlock(nn.Module):
         extent = radius * config.KP_extent / config.conv_radius
         self.block_name, self.layer_ind = block_name, layer_ind
         self.in_dim, self.out_dim = in_dim, out_dim
-        self.KPConv = KPConv(config.num_kernel_points, config.in_points_dim, in_dim, out_dim // 2,
-                             extent, radius, fixed_kernel_points=config.fixed_kernel_points,
-                             KP_influence=config.KP_influence,
-                             aggregation_mode=config.aggregation_mode,
-                             deformable='deform' in block_name, modulated=config.modulated)
+        self.KPConv = make_kpconv(block_name, config, in_dim, out_dim // 2, extent, radius)
         self.batch_norm = BatchNormBlock(out_dim // 2, config.use_batch_norm,
                                          config.batch_norm_momentum)
 
@@ -406,12 +496,7 @@ class ResnetBottleneckBlock(nn.Module):
         use_bn, mom = config.use_batch_norm, config.batch_norm_momentum
         self.unary1 = (UnaryBlock(in_dim, out_dim // 4, use_bn, mom) if in_dim != out_dim // 4
                        else nn.Identity())
-        self.KPConv = KPConv(config.num_kernel_points, config.in_points_dim, out_dim // 4,
-                             out_dim // 4, extent, radius,
-                             fixed_kernel_points=config.fixed_kernel_points,
-                             KP_influence=config.KP_influence,
-                             aggregation_mode=config.aggregation_mode,
-                             deformable='deform' in block_name, modulated=config.modulated)
+        self.KPConv = make_kpconv(block_name, config, out_dim // 4, out_dim // 4, extent, radius)
         self.batch_norm_conv = BatchNormBlock(out_dim // 4, use_bn, mom)
         self.res2net = my_res2Net(my_Bottle2neck, out_dim // 4, out_dim, baseWidth=14, scale=8)
         self.unary_shortcut = (UnaryBlock(in_dim, out_dim, use_bn, mom, no_relu=True)
@@ -440,9 +525,10 @@ class ResnetBottleneckBlock(nn.Module):
 
 def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config, flag=False):
     """finegrained_kpconv_blocks.py:414-460 (the block types of the reference configs)."""
-    if block_name == 'simple':
+    if block_name in ('simple', 'simple_deformable', 'simple_deformable_strided'):
         return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
-    if block_name in ('resnetb', 'resnetb_strided'):
+    if block_name in ('resnetb', 'resnetb_strided', 'resnetb_deformable',
+                      'resnetb_deformable_strided'):
         return ResnetBottleneckBlock(block_name, in_dim, out_dim, radius, layer_ind, config, flag)
     raise NotImplementedError(f'block {block_name!r} is not used by the reference configs')
 

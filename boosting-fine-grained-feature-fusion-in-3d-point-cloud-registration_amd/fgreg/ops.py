@@ -8,7 +8,7 @@ libfgreg.so, these raise.
 """
 import ctypes
 import math
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -426,6 +426,55 @@ def gather_bytes(idx, ns, cin, n_kp):
     nq, H = idx.shape
     v = int((idx < ns).sum().item())
     return nq * (8 * H + 12 + 4 * n_kp * cin + 4) + v * (12 + 4 * cin)
+
+
+def kpconv_deform_points(offset_raw, offset_nnorm, offset_bias, kernel_points, extent,
+                         modulated=False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """-> (kp_q (Nq, K, 3), mod (Nq, K) or None): the deformed kernel points and modulations of
+    blocks:270-306 from the offset KPConv's raw product (Nq, 3K; 4K when modulated), its
+    normaliser and offset_bias (fgr_kpconv_deform_points)."""
+    _dev(offset_raw, offset_nnorm, offset_bias, kernel_points)
+    raw, rn = _c(offset_raw, torch.float32), _c(offset_nnorm, torch.float32)
+    bias, kp = _c(offset_bias, torch.float32), _c(kernel_points, torch.float32)
+    nq, K = raw.shape[0], kp.shape[0]
+    assert raw.shape == (nq, (4 if modulated else 3) * K) and rn.shape == (nq,)
+    assert bias.shape == (raw.shape[1],) and kp.shape == (K, 3)
+    kp_q = torch.empty((nq, K, 3), dtype=torch.float32, device=raw.device)
+    mod = torch.empty((nq, K), dtype=torch.float32, device=raw.device) if modulated else None
+    _lib.check(_lib.load().fgr_kpconv_deform_points(_ptr(raw), _ptr(rn), _ptr(bias), _ptr(kp), nq, K,
+                                                    float(extent), _ptr(kp_q), _ptr(mod), _stream()),
+               'fgr_kpconv_deform_points')
+    return kp_q, mod
+
+
+def kpconv_gather_deform(q, s, idx, x, kp_q, mod, extent, influence='linear',
+                         aggregation='sum') -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (wf (Nq, K, Cin), nnorm (Nq,) f32) of the deformable KPConv's gather-weight stage
+    (blocks:296-385) under the per-query kernel points kp_q (Nq, K, 3) and modulations mod
+    (Nq, K) or None: neighbours out of every kernel point's range count as shadows
+    (fgr_kpconv_gather_deform). fp32 in every precision mode."""
+    inf, agg = kp_modes(influence, aggregation)
+    _dev(q, s, idx, x, kp_q, mod)
+    q, s, x = _c(q, torch.float32), _c(s, torch.float32), _c(x, torch.float32)
+    idx, kp_q = _c(idx, torch.int64), _c(kp_q, torch.float32)
+    mod = None if mod is None else _c(mod, torch.float32)
+    nq, ns = q.shape[0], s.shape[0]
+    assert idx.dim() == 2 and idx.shape[0] == nq and x.dim() == 2 and x.shape[0] == ns
+    assert kp_q.dim() == 3 and kp_q.shape[0] == nq and kp_q.shape[2] == 3
+    K, cin = kp_q.shape[1], x.shape[1]
+    assert mod is None or mod.shape == (nq, K)
+    wf = torch.empty((nq, K, cin), dtype=torch.float32, device=q.device)
+    nnorm = torch.empty((nq,), dtype=torch.float32, device=q.device)
+    nb = _lib.ws_size('fgr_kpconv_gather_deform_workspace', ns, cin)
+    ws = _workspace(q.device, nb) if nb else None
+    t0 = _begin('kpconv_gather_deform', (nq, idx.shape[1], cin, K))
+    _lib.check(_lib.load().fgr_kpconv_gather_deform(
+        _ptr(q), _ptr(s), nq, ns, _ptr(idx), idx.shape[1], _ptr(x), cin, _ptr(kp_q), _ptr(mod), K,
+        float(extent), inf, agg, _ptr(wf), _ptr(nnorm), _ptr(ws), nb, _stream()),
+        'fgr_kpconv_gather_deform')
+    _end('kpconv_gather_deform', t0,
+         lambda: gather_bytes(idx, ns, cin, K) + nq * K * (12 + (4 if mod is not None else 0)))
+    return wf, nnorm
 
 
 def max_pool(x, idx) -> torch.Tensor:

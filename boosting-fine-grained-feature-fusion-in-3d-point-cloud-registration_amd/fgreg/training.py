@@ -18,9 +18,10 @@ import torch.nn.functional as F
 
 from . import ops
 from . import linear as lin
-from .autograd import (attention_t, batchnorm_t, corr_attention_t, kpconv_t, layernorm_t, leaky,
-                       linear_t, max_pool_t, segnorm_t)
-from .backbone import ResnetBottleneckBlock, SimpleBlock, UnaryBlock, _level_inputs, host_layout
+from .autograd import (attention_t, batchnorm_t, corr_attention_t, kpconv_deform_t, kpconv_t,
+                       layernorm_t, leaky, linear_t, max_pool_t, segnorm_t)
+from .backbone import (DeformableKPConv, ResnetBottleneckBlock, SimpleBlock, UnaryBlock,
+                       _level_inputs, host_layout)
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
 from .transformer import PositionEmbeddingLearned
 
@@ -69,17 +70,24 @@ def bottle2neck_train(m, x):
     return batchnorm_t(m.bn3, linear_t(cat, m.conv3.weight), residual=res, post_act=ACT_RELU)
 
 
+def _conv_train(conv, q, s, idx, x):
+    """A block's KPConv, rigid or deformable -> (unnormalised output, nnorm)."""
+    if isinstance(conv, DeformableKPConv):
+        return kpconv_deform_t(conv, q, s, idx, x)
+    return kpconv_t(conv, q, s, idx, x)
+
+
 def block_train(block, x, meta):
     q, s, idx, post = _level_inputs(block.block_name, block.layer_ind, meta)
     if isinstance(block, SimpleBlock):                         # blocks:620-634
         lens, off = host_layout(meta, post)
-        y, nnorm = kpconv_t(block.KPConv, q, s, idx, x)
+        y, nnorm = _conv_train(block.KPConv, q, s, idx, x)
         return segnorm_t(y, off, lens, row_div=nnorm, act=ACT_LEAKY)
     assert isinstance(block, ResnetBottleneckBlock)            # blocks:692-727
     lens_pre, off_pre = host_layout(meta, block.layer_ind)
     lens_post, off_post = host_layout(meta, post)
     x1 = unary_train(block.unary1, x, off_pre, lens_pre) if isinstance(block.unary1, UnaryBlock) else x
-    y, nnorm = kpconv_t(block.KPConv, q, s, idx, x1)
+    y, nnorm = _conv_train(block.KPConv, q, s, idx, x1)
     y = segnorm_t(y, off_post, lens_post, row_div=nnorm)
     # res2net ends in ReLU: the LeakyReLU at :715 is the identity, gradient included
     y = bottle2neck_train(block.res2net.layer1[0], y)

@@ -158,6 +158,51 @@ int fgr_kpconv_gather_mode(const float* q, const float* s, int64_t nq, int64_t n
                            int32_t aggregation, float* wf, float* nnorm, void* workspace,
                            size_t ws_bytes, void* stream);
 
+/* Deformable (and modulated) KPConv, the `deformable` branch of KPConv.forward (:270-345,
+ * :384-385). A rigid offset KPConv (fgr_kpconv_gather_mode + the weight GEMM) gives the raw
+ * offset product (nq, 3K; 4K when modulated) and its normaliser.
+ *  fgr_kpconv_deform_points  with f = offset_raw / offset_nnorm + offset_bias:
+ *      kp_q[q, k, :] = kp[k] + extent * f[q, 3k : 3k + 3]            (nq, K, 3)
+ *      mod[q, k]     = 2 sigmoid(f[q, 3K + k])                       (nq, K)
+ *    mod == NULL: not modulated (offset_raw has 3K columns, else 4K).
+ *  fgr_kpconv_gather_deform  fgr_kpconv_gather_mode under every query's own kernel points, with
+ *    d2[q, h, k] = |(s[idx[q,h]] - q) - kp_q[q, k]|^2. A valid neighbour is IN RANGE iff
+ *    d2 < extent^2 for some k; one that is not is a shadow (the reference's topk re-indexing,
+ *    :319-343, without its host readback):
+ *      wf[q, k, c] = mod[q, k] * sum_{in-range h} w(d2[q, h, k]) x[idx[q,h], c]   (mod NULL: 1)
+ *      nnorm[q]    = max(1, #{in-range h : sum_c x[idx[q,h], c] > 0})
+ *    The widths, n_kp, modes and refusals of fgr_kpconv_gather_mode; x and wf 16-B aligned at
+ *    cin 128 / 256. workspace: fgr_kpconv_gather_deform_workspace() bytes.
+ *  fgr_kpconv_scatter_deform  dx (ns, cin) of that gather from dwf (nq, K * cin) over the CSR
+ *    inverse of fgr_nbr_inverse, as fgr_kpconv_scatter_mode; the in-range mask is a constant.
+ *  fgr_kpconv_deform_grad    d_kp (nq, K, 3) and d_mod (nq, K; NULL: skipped) of that gather from
+ *    dwf: through w into kp_q (none under FGR_KP_CONSTANT: exact zeros; 0 at d2 = 0, where the
+ *    reference's sqrt has no derivative) and through mod. The in-range mask and the closest
+ *    one-hot are constants. One wave owns each (q, k): no atomics, bit-reproducible.
+ * Every entry point checks its arguments before anything is launched or written: a bad mode,
+ * cin, n_kp or extent returns FGR_E_ARG and fgr_last_error names the entry point and the value. */
+int fgr_kpconv_deform_points(const float* offset_raw, const float* offset_nnorm,
+                             const float* offset_bias, const float* kp, int64_t nq, int32_t n_kp,
+                             float extent, float* kp_q, float* mod, void* stream);
+int fgr_kpconv_gather_deform_workspace(int64_t ns, int32_t cin, size_t* bytes);
+int fgr_kpconv_gather_deform(const float* q, const float* s, int64_t nq, int64_t ns,
+                             const int64_t* idx, int32_t width, const float* x, int32_t cin,
+                             const float* kp_q, const float* mod, int32_t n_kp, float extent,
+                             int32_t influence, int32_t aggregation, float* wf, float* nnorm,
+                             void* workspace, size_t ws_bytes, void* stream);
+int fgr_kpconv_scatter_deform_workspace(int64_t nq, int32_t width, int32_t cin, size_t* bytes);
+int fgr_kpconv_scatter_deform(const float* q, const float* s, int64_t nq, int64_t ns,
+                              const int64_t* idx, int32_t width, const float* dwf, int32_t cin,
+                              const float* kp_q, const float* mod, int32_t n_kp, float extent,
+                              int32_t influence, int32_t aggregation, const int32_t* start,
+                              const int32_t* pos, float* dx, void* ws, size_t ws_bytes,
+                              void* stream);
+int fgr_kpconv_deform_grad(const float* q, const float* s, int64_t nq, int64_t ns,
+                           const int64_t* idx, int32_t width, const float* x, int32_t cin,
+                           const float* dwf, const float* kp_q, const float* mod, int32_t n_kp,
+                           float extent, int32_t influence, int32_t aggregation, float* d_kp,
+                           float* d_mod, void* stream);
+
 /* max_pool (finegrained_kpconv_blocks.py:125-141): out[q, c] = max over the row of
  * x[idx[q, h], c], shadow entries contributing 0 (the appended zero row). */
 int fgr_max_pool(const float* x, int64_t ns, int32_t c, const int64_t* idx, int64_t nq,

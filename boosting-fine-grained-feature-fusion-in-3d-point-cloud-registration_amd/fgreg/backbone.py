@@ -33,6 +33,10 @@ from . import linear as lin
 from . import ops
 from .linear import linear
 
+# the Res2Net bottleneck's conv1 inside the hierarchy launch where an instance exists
+# (ops.res2net_block_supported) and the forward runs in f16x3 (False: conv1 GEMM + chain)
+R2N_FUSED = True
+
 
 # ------------------------------------------------------------------------------------------
 # Preprocessing
@@ -397,6 +401,10 @@ class my_Bottle2neck(nn.Module):  # noqa: N801 -- reference name (res2net.py:84)
                         chain = (bst, ops.res2net_fragments3(wst), None)
                     elif ops.res2net_chain_supported(self.width, True):
                         chain = (bst,) + ops.res2net_fragments_h3(wst)
+                    # conv1's image for the one-launch front (fgr_res2net_block_h3 / block6)
+                    if chain is not None and ops.res2net_block_supported(
+                            self.width, w1.shape[1], chain[2] is not None):
+                        chain = chain + ops.res2net_conv1_fragments(w1, self.scale)
             self._folded = (key, w1, b1, ws, w3d, b3d, chain)
             ops.note_state(w1, b1, w3d, b3d, *[t for wb in ws for t in wb],
                            *(chain if chain is not None else ()))
@@ -411,12 +419,18 @@ class my_Bottle2neck(nn.Module):  # noqa: N801 -- reference name (res2net.py:84)
             y = bottle2neck_train(self, x)
             return y if shortcut is None else F.leaky_relu(y + shortcut, 0.1)
         w1, b1, ws, w3d, b3d, chain = self._folded_params()
-        out = linear(x, w1, b1, act=ops.ACT_RELU)
         w = self.width
         down = self.downsample is not None
         cat_in = torch.empty((x.shape[0], w * self.scale + (x.shape[1] if down else 0)),
                              dtype=x.dtype, device=x.device)
-        if chain is not None:
+        fused = R2N_FUSED and chain is not None and len(chain) == 5 and lin.MODE == 'f16x3'
+        if not fused:
+            out = linear(x, w1, b1, act=ops.ACT_RELU)
+        if fused:
+            # conv1 + the hierarchy + the [.. | x] concat in one launch: h is never written
+            ops.res2net_block(x, w, self.scale, chain[3], chain[4], b1, chain[1], chain[0],
+                              cat_in, w_scale=chain[2])
+        elif chain is not None:
             # one launch for the whole hierarchy + the [.. | x] concat (fgr_res2net_chain*)
             ops.res2net_chain(out, w, self.scale, chain[1], chain[0], x, cat_in, w_scale=chain[2])
         else:

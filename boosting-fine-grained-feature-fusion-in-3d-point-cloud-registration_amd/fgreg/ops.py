@@ -679,6 +679,72 @@ def res2net_chain(h, w, scale, w_frag, bias, x, cat, w_scale=None):
     return cat
 
 
+def res2net_conv1_fragments(w1: torch.Tensor, scale: int = 1):
+    """(scale * w, cin) conv1 weights (out, in), cin % 32 == 0 -> (image, inverse scales) of
+    fgr_res2net_block_h3: each output row n scaled by 2^e so its max |w| lies in
+    [2^14, 2^15) (e = 0 for an all-zero row; w1sc[n] = 2^-e), each of the ``scale`` chunks of w
+    rows zero-padded to KT = ceil(w / 16) whole 16-row tiles, split into two fp16 terms
+    (h = f16(x), m = f16(x - h), round to nearest), in 16x16x32 fragment order
+    [jt][ks][term][g][c][8], jt = j * KT + tile, with value
+    W1[j * w + 16 tile + c][32 ks + 8 g + e] * 2^e_row (0 where 16 tile + c >= w). ``scale``
+    only matters when w % 16 != 0 (the per-chunk padding)."""
+    rows, cin = w1.shape
+    w = rows // scale
+    assert rows == scale * w and cin % 32 == 0
+    kt = (w + 15) // 16
+    mx = w1.abs().amax(dim=1)
+    e = torch.where(mx > 0, 15 - torch.frexp(mx).exponent, torch.zeros_like(mx, dtype=torch.int32))
+    e = e.clamp(max=127)
+    sc = torch.ldexp(torch.ones_like(mx), e.float())
+    wp = torch.zeros((scale, kt * 16, cin), dtype=torch.float32, device=w1.device)
+    wp[:, :w] = (w1 * sc[:, None]).reshape(scale, w, cin)
+    hi = wp.to(torch.float16)
+    lo = (wp - hi.float()).to(torch.float16)
+    t = torch.stack([hi, lo], 0).reshape(2, scale * kt, 16, cin // 32, 4, 8)
+    img = t.permute(1, 3, 0, 4, 2, 5).contiguous()                    # [jt, ks, t, g, c, e]
+    return img, (1.0 / sc).contiguous()
+
+
+def res2net_block_supported(w, cin, h3=True):
+    """(w, cin) pairs with a fused conv1 + hierarchy instance: fgr_res2net_block_h3 (h3) at
+    (28, 32), (56, 64), (112, 128) and w % 4 == 0 within the same 16-column tile counts;
+    fgr_res2net_block6 (the bf16x6 hierarchy) at (224, 256)."""
+    if not h3:
+        return (w, cin) == (224, 256)
+    return w > 0 and w % 4 == 0 and ((w + 15) // 16, cin) in ((2, 32), (4, 64), (7, 128))
+
+
+def res2net_block(x, w, scale, w1_img, w1_scale, b1, w_frag, bias, cat, w_scale=None):
+    """cat[:, :] = [sp_0..sp_{scale-2} | h_{scale-1} | x] from x in one launch: conv1 (+ folded
+    BN + ReLU) computed chunk by chunk inside the hierarchy kernel, h never written.
+    (w1_img, w1_scale) = res2net_conv1_fragments; fgr_res2net_block_h3 with (w_frag, w_scale) =
+    res2net_fragments_h3 or, when w_scale is None, fgr_res2net_block6 with w_frag =
+    res2net_fragments3."""
+    _dev(x, w1_img, w1_scale, b1, w_frag, w_scale, bias, cat)
+    x = _c(x, torch.float32)
+    n, cin = x.shape
+    h3 = w_scale is not None
+    if not res2net_block_supported(w, cin, h3):
+        raise _lib.FgrError(f'res2net_block: no fused instance for w {w}, cin {cin}, '
+                            f'{"f16x3" if h3 else "bf16x6"}')
+    assert cat.shape[0] == n and cat.stride(1) == 1
+    L = _lib.load()
+    # MFMA work: the hierarchy's (as res2net_chain) plus conv1's three fp16 products
+    t0 = _begin('res2net', 'h3' if h3 else 'x6')
+    work = 2 * n * w * w * (scale - 1) * (3 if h3 else 6) + 3 * 2 * n * cin * scale * w
+    if h3:
+        _lib.check(L.fgr_res2net_block_h3(
+            _ptr(x), n, w, cin, scale, _ptr(w1_img), _ptr(w1_scale), _ptr(b1), _ptr(w_frag),
+            _ptr(w_scale), _ptr(bias), _ptr(cat), cat.stride(0), _stream()),
+            'fgr_res2net_block_h3')
+    else:
+        _lib.check(L.fgr_res2net_block6(
+            _ptr(x), n, w, cin, scale, _ptr(w1_img), _ptr(w1_scale), _ptr(b1), _ptr(w_frag),
+            _ptr(bias), _ptr(cat), cat.stride(0), _stream()), 'fgr_res2net_block6')
+    _end('res2net', t0, work)
+    return cat
+
+
 # ------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------

@@ -280,6 +280,35 @@ int fgr_res2net_chain_h3(const float* h, int64_t n, int32_t w, int32_t scale, co
                          const float* w_scale, const float* bias, const float* x, int32_t cin,
                          float* cat, int64_t ld_cat, void* stream);
 
+/* The bottleneck front in one launch (f16x3): conv1 + the hierarchy + the concat, from x:
+ *   h_j  = ReLU(W1_j x + b1_j)                        j < scale   (never stored, except the
+ *   sp_i = ReLU(W_i (sp_{i-1} + h_i) + b_i)           i < scale-1  pass-through h_{scale-1})
+ *   cat  = [sp_0 .. sp_{scale-2} | h_{scale-1} | x]
+ * x (n, cin) contiguous, cat (n, ld_cat), ld_cat >= scale*w + cin and ld_cat % 4 == 0.
+ * conv1 follows fgr_gemm_f16x3's row-stationary recipe: one exact power-of-two scale per row
+ * of x, two fp16 terms, W1 pre-scaled per output row. w1_img = fgreg.ops.res2net_conv1_fragments
+ * image [jt = j*KT + tile][ks][term 2][g][c][8] (fp16; KT = ceil(w / 16) tiles per chunk, each
+ * chunk zero-padded to whole tiles; ks < cin / 32) with value
+ * W1[j*w + 16 tile + c][32 ks + 8 g + e] * 2^e_row; w1_scale (scale*w) its inverse scales,
+ * b1 (scale*w); w_img / w_scale / bias as fgr_res2net_chain_h3. Instances (w, cin): (28, 32),
+ * (56, 64), (112, 128) -- w % 4 == 0 within the same tile counts; any other pair is refused
+ * (224, 256) has fgr_res2net_block6 below.
+ * Every pointer 16-B aligned. */
+int fgr_res2net_block_h3(const float* x, int64_t n, int32_t w, int32_t cin, int32_t scale,
+                         const void* w1_img, const float* w1_scale, const float* b1,
+                         const void* w_img, const float* w_scale, const float* bias, float* cat,
+                         int64_t ld_cat, void* stream);
+
+/* The same front on the bf16x6 hierarchy (fgr_res2net_chain6's arithmetic for the chain,
+ * conv1 in f16x3 as in fgr_res2net_block_h3, from the same w1_img / w1_scale / b1): the one
+ * instance is (w, cin) = (224, 256), any other pair is refused. w_img / bias as
+ * fgr_res2net_chain6. x, cat and both images 16-B aligned, ld_cat % 4 == 0. Rows per block
+ * (16 / 32 / 48) by row count as fgr_res2net_chain6; the result does not depend on it. */
+int fgr_res2net_block6(const float* x, int64_t n, int32_t w, int32_t cin, int32_t scale,
+                       const void* w1_img, const float* w1_scale, const float* b1,
+                       const void* w_img, const float* bias, float* cat, int64_t ld_cat,
+                       void* stream);
+
 /* ---- dense layers ----------------------------------------------------------------------
  * Every Linear / KPConv-weight product of the forward:
  *   C[m, n] = act(A[m, :] . W[n, :] + bias[n] (+ R[m, n]))

@@ -183,6 +183,9 @@ SIGNATURES = {
     'fgr_crop_pairs_mask': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'fgr_crop_pairs_assemble': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                 _vp, _vp],
+    'fgr_augment_workspace_bytes': [_i64, _i32, ctypes.POINTER(_sz)],
+    'fgr_augment_pairs': [_vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                          _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
 }
 
 NB_INDEX, NB_DIST = 0, 1

@@ -9,7 +9,7 @@
   correspondence is mutual only if both directions agree AND the source's partner index is
   > 0 (``src_corr > 0``, pointcloud.py:57), so target point 0 never appears in it.
 * ``ThreeDMatchPairs`` mirrors ``ThreeDMatchDataset.__getitem__`` (threedmatch.py:65-107)
-  for the test phase: pose from the info dict's rot / trans (src -> tgt), the two fragment
+  for the test phase, and with ``transforms`` for the train phase: pose from the info dict's rot / trans (src -> tgt), the two fragment
   files, overlap masks and mutual correspondences (from a precomputed ``pairs`` mapping when
   given, else ``compute_overlap`` on the GPU), with the same keys. The info dict is passed in
   (the reference unpickles ``datasets/3dmatch/<phase>_<benchmark>_info.pkl``; reading that
@@ -82,12 +82,16 @@ class ThreeDMatchPairs(torch.utils.data.Dataset):
     """Test-phase 3DMatch / 3DLoMatch pairs with the keys of ThreeDMatchDataset
     (threedmatch.py:65-107). ``infos``: dict with lists 'rot' (3,3), 'trans' (3,1 or 3),
     'src', 'tgt' (paths relative to ``root``), 'overlap'; ``pairs``: optional mapping
-    item -> (src_mask, tgt_mask, src_tgt_corr) (the precomputed h5 content)."""
+    item -> (src_mask, tgt_mask, src_tgt_corr) (the precomputed h5 content); ``transforms``:
+    optional callable sample -> sample for the train phase (fgreg.augment.TrainAugment, what
+    get_dataloader composes from perturb_pose / augment_noise)."""
 
-    def __init__(self, root, infos, overlap_radius=0.0375, device='cuda', pairs=None):
+    def __init__(self, root, infos, overlap_radius=0.0375, device='cuda', pairs=None,
+                 transforms=None):
         self.root, self.infos, self.radius = root, infos, float(overlap_radius)
         self.device = torch.device(device)
         self.pairs = pairs
+        self.transforms = transforms
 
     def __len__(self):
         return len(self.infos['rot'])
@@ -111,7 +115,10 @@ class ThreeDMatchPairs(torch.utils.data.Dataset):
             p64 = torch.from_numpy(pose).to(self.device)
             src_w = (src_xyz.to(self.device, torch.float64) @ p64[:, :3].T + p64[:, 3]).float()
             sm, tm, corr = compute_overlap(src_w, tgt, self.radius)
-        return {'src_xyz': src, 'tgt_xyz': tgt, 'src_overlap': sm, 'tgt_overlap': tm,
-                'correspondences': corr, 'pose': pose_t, 'idx': item,
-                'src_path': self.infos['src'][item], 'tgt_path': self.infos['tgt'][item],
-                'overlap_p': self.infos['overlap'][item]}
+        sample = {'src_xyz': src, 'tgt_xyz': tgt, 'src_overlap': sm, 'tgt_overlap': tm,
+                  'correspondences': corr, 'pose': pose_t, 'idx': item,
+                  'src_path': self.infos['src'][item], 'tgt_path': self.infos['tgt'][item],
+                  'overlap_p': self.infos['overlap'][item]}
+        if self.transforms is not None:               # training augmentation, applied last
+            sample = self.transforms(sample)          # (threedmatch.py:103-104)
+        return sample

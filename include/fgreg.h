@@ -670,6 +670,44 @@ int fgr_crop_pairs_assemble(const float* raw, int32_t ld, const int64_t* offsets
                             const double* noise, const float* rt, int32_t m, float* xyz,
                             uint8_t* overlap, int64_t* corr, int32_t* n_corr, void* stream);
 
+/* ---- Input side: the 3DMatch / MCD training augmentations on the GPU -----------------------
+ * data_loaders/transforms.py RigidPerturb (:15-72), Jitter (:75-92), ShufflePoints (:95-131)
+ * and RandomSwap (:134-151) as data_loaders/__init__.py:16-57 chains them, for a batch of
+ * n_pairs samples; the random draws stay in the reference's streams on the host
+ * (fgreg/augment.py). Every output is evaluated in float64 and rounded once.
+ * Layout: the clouds are 2 n_pairs packed segments, the source of pair b (segment 2b), then
+ * its target (2b + 1). in_off (2 n_pairs + 1) are their row offsets in xyz (ld floats per row,
+ * xyz first), overlap (one byte per row) and noise (nullable; 3 float32 per row, already
+ * scaled); n_points = in_off[2 n_pairs]. perm holds, per INPUT segment at out_off
+ * (2 n_pairs + 1), the kept raw rows in output order (distinct, < the cloud's size: the caller
+ * validates them); max_out >= the longest of them. corr / corr_out are (2, corr_ld) int64 with
+ * pair b's columns at [corr_off[b], corr_off[b + 1]) (n_pairs + 1 offsets; corr may be NULL
+ * when corr_ld is 0). pose / perturb / pose_out are (n_pairs, 3, 4) float32. flags[b] is a sum
+ * of FGR_AUG_*: PERTURB (perturb[b] applies), SOURCE (to the source; else to the target),
+ * CENTRE (about the perturbed cloud's centroid, C^-1 P C: the 'small' mode), SWAP.
+ *   pose_out[b]    pose . P^-1 (source perturbed) or P . pose, inverted under SWAP
+ *   xyz_out        row out_off[s] + i of the cloud that ends as segment s:
+ *                  T raw[perm[i]] + noise[perm[i]] (T = P of the perturbed cloud, else I)
+ *   overlap_out    overlap[perm[i]], same rows
+ *   corr_out       the columns of corr whose two points were both kept, as output rows, in
+ *                  their original order (rows exchanged under SWAP), n_corr[b] of them
+ * Outputs are in post-swap order: under SWAP the target's rows come first in pair b's span
+ * (and are the new source). A correspondence index outside its cloud is never dereferenced:
+ * n_corr[b] = -1 for that pair. ws: fgr_augment_workspace_bytes(n_points, n_pairs) bytes,
+ * 8-B aligned. Three launches on `stream`, no host sync; results are run-to-run identical. */
+#define FGR_AUG_PERTURB 1
+#define FGR_AUG_SOURCE 2
+#define FGR_AUG_CENTRE 4
+#define FGR_AUG_SWAP 8
+int fgr_augment_workspace_bytes(int64_t n_points, int32_t n_pairs, size_t* bytes);
+int fgr_augment_pairs(const float* xyz, int32_t ld, const int64_t* in_off, int64_t n_points,
+                      const uint8_t* overlap, const int64_t* corr, int64_t corr_ld,
+                      const int64_t* corr_off, const float* pose, const float* perturb,
+                      const int32_t* flags, const int32_t* perm, const int64_t* out_off,
+                      int32_t max_out, const float* noise, int32_t n_pairs, float* xyz_out,
+                      uint8_t* overlap_out, int64_t* corr_out, int32_t* n_corr, float* pose_out,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* The pre-norm layer's in_proj with the attention's K / V images written in its epilogue
  * (transformers.py:193-196 / :213-221 + the image building of fgr_attention_f16x3, head dim 32):
  * qkv = (LayerNorm(x) * gamma + beta + add) W^T + bias as fgr_gemm_f16x3_ln, but only the q

@@ -110,8 +110,10 @@ class PreprocessorHIP(nn.Module):
                 conv_i = torch.zeros((0, 1), dtype=torch.int64, device=device)
             if 'pool' in block or 'strided' in block:
                 dl = 2 * r_normal / cfg.conv_radius
-                pool_p, pool_lens, pool_len_dev, pool_off = ops.grid_subsample(points, off, lens, dl,
-                                                                               device_layout=True)
+                # 'auto': large-extent clouds (mcd.yaml's lidar sweeps at a 5 cm voxel) leave the
+                # dense voxel histogram for the radix-sorted path; same bits either way
+                pool_p, pool_lens, pool_len_dev, pool_off = ops.grid_subsample(
+                    points, off, lens, dl, device_layout=True, sparse='auto')
                 r_pool = r_deform if 'deformable' in block else r_normal
                 if r_pool != r:
                     r = r_pool

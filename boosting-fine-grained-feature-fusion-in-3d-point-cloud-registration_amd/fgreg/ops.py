@@ -200,10 +200,66 @@ def offsets(lengths: Sequence[int], device) -> torch.Tensor:
 # geometry
 # ------------------------------------------------------------------------------------------
 GRID_MAX_CELLS = 1 << 28     # dense voxel histogram ceiling (1 GiB of counters)
+# sparse='auto' leaves the dense counting sort for the radix-sorted path (fgr_grid_subsample_
+# sparse_*) once the clouds' summed key space exceeds this many cells. Results are bit-identical
+# on either side of it. Measured on 20k + 20k indoor points stretched by one far point (MI355X,
+# DESIGN.md "Grid subsampling"): the dense retry has to clear and scan `cells` counters and
+# wins at 2^22 cells (0.155 ms against 0.192 ms, both after the failed first attempt), the
+# sort's cost follows the point count and wins from 2^24 on (0.188 against 0.205 ms; 0.21
+# against 1.53 ms at 2^28).
+GRID_SPARSE_FROM = 1 << 24
+GRID_SPARSE_TILE = 1024      # items per block of the sparse path's radix sort (kRT, grid_sparse.hip)
+_SPARSE_ERRORS = {-1: 'a cloud has more than 2^20 voxels along an axis',
+                  -2: 'the summed key space reaches 2^62 cells',
+                  -3: 'key_bits is smaller than the summed key space needs'}
+
+
+def _grid_result(out, host, counts, keys, nc, return_keys, device_layout):
+    if device_layout:
+        assert not return_keys
+        len_dev = counts[:nc]
+        off_dev = lengths_to_offsets(len_dev)
+        return out, host[:nc], len_dev, off_dev
+    if return_keys:
+        return out, host[:nc], keys
+    return out, host[:nc]
+
+
+def _grid_subsample_sparse(pts, off, nc, dl, key_bits, return_keys, device_layout):
+    """The radix-sorted path of grid_subsample: scratch and time follow the number of points,
+    not the clouds' extent. ``key_bits``: 0 or an upper bound on the bits of the summed key
+    space (only that many bytes are sorted)."""
+    n = pts.shape[0]
+    L = _lib.load()
+    counts = torch.empty(nc + 1, dtype=torch.int64, device=pts.device)
+    st = _stream()
+    ws_bytes = _lib._sz(0)
+    _lib.check(L.fgr_grid_subsample_sparse_workspace(n, nc, ws_bytes),
+               'fgr_grid_subsample_sparse_workspace')
+    ws = scratch(pts.device, ws_bytes.value)
+    t0 = _begin('grid_subsample')
+    _lib.check(L.fgr_grid_subsample_sparse_count(_ptr(pts), _ptr(off), nc, n, float(dl),
+                                                 int(key_bits), _ptr(ws), ws_bytes.value,
+                                                 _ptr(counts), st),
+               'fgr_grid_subsample_sparse_count')
+    _end('grid_subsample', t0)
+    host = counts.cpu().tolist()  # host sync: output size is data-dependent
+    m = host[nc]
+    if m < 0:
+        raise _lib.FgrError(f'grid subsampling: the clouds\' voxel key space at dl = {dl} is past '
+                            f'the sparse path\'s limit: {_SPARSE_ERRORS.get(m, m)}')
+    out = torch.empty((m, 3), dtype=torch.float32, device=pts.device)
+    keys = torch.empty((m,), dtype=torch.int64, device=pts.device) if return_keys else None
+    t0 = _begin('grid_subsample')
+    _lib.check(L.fgr_grid_subsample_sparse_fill(n, nc, m, _ptr(ws), ws_bytes.value, _ptr(pts),
+                                                _ptr(out), _ptr(keys), st),
+               'fgr_grid_subsample_sparse_fill')
+    _end('grid_subsample', t0, 12 * (n + m))   # D4: 12 (N_in + N_out) bytes
+    return _grid_result(out, host, counts, keys, nc, return_keys, device_layout)
 
 
 def grid_subsample(points: torch.Tensor, off: torch.Tensor, lengths: Sequence[int], dl: float,
-                   return_keys=False, max_cells=None, device_layout=False):
+                   return_keys=False, max_cells=None, device_layout=False, sparse=False):
     """Barycentre grid subsampling per cloud (grid_subsampling.cpp semantics).
 
     Returns (sub_points (M,3) f32, sub_lengths List[int][, keys (M,) int64]). One host
@@ -211,14 +267,23 @@ def grid_subsample(points: torch.Tensor, off: torch.Tensor, lengths: Sequence[in
     voxel-key histogram's capacity (None = the library default); a key space past it is
     reported by the count call and the count is redone with the needed capacity, up to
     GRID_MAX_CELLS (2^28 cells: a 645-voxel cube per cloud, 16 m at 3DMatch's 2.5 cm); past
-    that it raises. ``device_layout``: also return
+    that it raises unless ``sparse`` says otherwise. ``device_layout``: also return
     the sub-clouds' lengths (nc,) and row offsets (nc + 1,) as device int64 tensors, built on
     the device from the counts (no host -> device copy): (sub, lengths, len_dev, off_dev).
+    ``sparse``: False (default) -- the dense counting sort only; 'auto' -- the dense attempt
+    first and, when the key space it reports exceeds GRID_SPARSE_FROM, the radix-sorted path
+    (fgr_grid_subsample_sparse_*: any extent up to 2^20 voxels per axis and 2^62 cells in all)
+    instead of the retry or the raise; True -- always the radix-sorted path. The three return
+    the same bits.
     """
+    if not (sparse is False or sparse is True or sparse == 'auto'):
+        raise ValueError(f"sparse must be False, True or 'auto', got {sparse!r}")
     _dev(points, off)
     pts = _c(points, torch.float32)
     n, nc = pts.shape[0], len(lengths)
     assert pts.dim() == 2 and pts.shape[1] == 3 and off.numel() == nc + 1
+    if sparse is True:
+        return _grid_subsample_sparse(pts, off, nc, dl, 0, return_keys, device_layout)
     L = _lib.load()
     cap = 0 if max_cells is None else int(max_cells)
     counts = torch.empty(nc + 1, dtype=torch.int64, device=pts.device)
@@ -237,6 +302,10 @@ def grid_subsample(points: torch.Tensor, off: torch.Tensor, lengths: Sequence[in
         if host[nc] >= 0:
             break
         need = -host[nc]           # dense key space past the histogram: retry once
+        if sparse == 'auto' and need > GRID_SPARSE_FROM:
+            del ws
+            return _grid_subsample_sparse(pts, off, nc, dl, min(need.bit_length(), 62),
+                                          return_keys, device_layout)
         if need > GRID_MAX_CELLS:
             raise _lib.FgrError(f'grid subsampling: the clouds\' voxel key space ({need} cells at '
                                 f'dl = {dl}) exceeds the dense histogram limit {GRID_MAX_CELLS}')
@@ -249,14 +318,7 @@ def grid_subsample(points: torch.Tensor, off: torch.Tensor, lengths: Sequence[in
     _lib.check(L.fgr_grid_subsample_fill(n, nc, cap, m, _ptr(ws), ws_bytes.value, _ptr(pts),
                                          _ptr(out), _ptr(keys), st), 'fgr_grid_subsample_fill')
     _end('grid_subsample', t0, 12 * (n + m))   # D4: 12 (N_in + N_out) bytes
-    if device_layout:
-        assert not return_keys
-        len_dev = counts[:nc]
-        off_dev = lengths_to_offsets(len_dev)
-        return out, host[:nc], len_dev, off_dev
-    if return_keys:
-        return out, host[:nc], keys
-    return out, host[:nc]
+    return _grid_result(out, host, counts, keys, nc, return_keys, device_layout)
 
 
 def lengths_to_offsets(len_dev: torch.Tensor) -> torch.Tensor:

@@ -23,6 +23,9 @@ clouds of the same shape as the reference's test inputs:
 * ``lowoverlap_pair(i)`` -- a 3DLoMatch-like pair (BASELINE configs[4]): two fragments cut
   from opposite ends of a 6 x 3 x 2.5 m room so that 10-30% of each fragment lies in the
   shared strip, each sampled independently with N points, plus the same random motion.
+* ``lidar_like_pair(i)`` -- an MCD-like outdoor sweep pair: 6000 points per cloud over
+  60 x 60 x 12 m (a ground disc plus walls and poles), whose voxel key space at a 5 cm voxel
+  is past the dense grid-subsampling histogram (the sparse path's test input).
 """
 import math
 
@@ -158,6 +161,41 @@ def lowoverlap_pair(i, n_points=20000, overlap=(0.1, 0.3), max_rot_deg=15.0, max
     src = (src0 - t) @ R
     pose = np.concatenate([R, t[:, None]], 1)
     return src.astype(np.float32), tgt.astype(np.float32), pose.astype(np.float32), f
+
+
+def _lidar_sweep(rng, n, extent):
+    """n points of an outdoor-lidar-like sweep inside ``extent`` (x, y, z spans in metres): a
+    ground disc of radius extent / 2 (2 cm height noise) and, for the first third of the rows,
+    walls and poles: heights up to the z extent on planes 7 m apart in x."""
+    r_max = 0.5 * min(extent[0], extent[1])
+    rad = rng.uniform(1.0, r_max, n)
+    th = rng.uniform(0.0, 2.0 * math.pi, n)
+    g = np.stack([rad * np.cos(th), rad * np.sin(th), rng.normal(0.0, 0.02, n)], 1)
+    k = n // 3
+    g[:k, 2] = rng.uniform(0.0, extent[2], k)
+    g[:k, 0] = np.round(g[:k, 0] / 7.0) * 7.0
+    return g.astype(np.float32)
+
+
+def lidar_like_pair(i, n_points=6000, extent=(60.0, 60.0, 12.0)):
+    """An MCD-like outdoor sweep pair: n_points per cloud spread over ``extent`` metres, far
+    sparser than an indoor fragment -- at mcd.yaml's first pooling voxel (dl = 0.05) the pair's
+    dense voxel key space is 6.9e8 cells, past fgreg.ops.GRID_MAX_CELLS. The two sweeps are
+    independent draws; the source is the second one moved by a random rotation <= 15 deg about
+    a near-vertical axis (a vehicle's yaw, so the extent stays what ``extent`` says) and a
+    translation <= 0.3 m. Returns (src (N,3) f32, tgt (N,3) f32, pose (3,4) f32: src -> tgt)."""
+    tgt = _lidar_sweep(np.random.default_rng(15485863 * (i + 1)), n_points, extent)
+    src0 = _lidar_sweep(np.random.default_rng(15485863 * (i + 1) + 1), n_points, extent)
+    rng = np.random.default_rng(15485863 * (i + 1) + 2)
+    axis = np.array([rng.normal(0.0, 0.02), rng.normal(0.0, 0.02), 1.0])
+    axis /= np.linalg.norm(axis)
+    ang = np.deg2rad(rng.uniform(0, 15.0))
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    R = np.eye(3) + math.sin(ang) * K + (1 - math.cos(ang)) * K @ K
+    t = rng.uniform(-0.3, 0.3, 3)
+    src = (src0.astype(np.float64) - t) @ R
+    pose = np.concatenate([R, t[:, None]], 1)
+    return src.astype(np.float32), tgt, pose.astype(np.float32)
 
 
 def modelnet_reference_pair(i, n_raw=2048):

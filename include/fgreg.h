@@ -61,7 +61,7 @@ const char* fgr_last_error(void);
 /* Opt-in instrumentation (bench.py's per-kernel rooflines; not part of the reference's
  * interface): arms two caller-created hipEvent_t for the NEXT timed entry point called on
  * this thread (fgr_kpconv_gather, fgr_attention*, fgr_gemm_f16x3, fgr_gemm_bf16,
- * fgr_grid_subsample_count / _fill, fgr_radius_search,
+ * fgr_grid_subsample_count / _fill, fgr_grid_subsample_sparse_count / _fill, fgr_radius_search,
  * fgr_radius_grid_build, fgr_radius_search_grid, fgr_instnorm, fgr_layernorm,
  * fgr_pair_pose). That call records `start_event` on its stream right before its
  * first kernel launch and `end_event` after its last one, then disarms; (NULL, NULL)
@@ -76,7 +76,8 @@ int fgr_time_next_call(void* start_event, void* end_event);
  * emitted in ascending key order per cloud, members summed in ascending point index.
  * `max_cells`: a counting sort over a dense voxel-key histogram of that many counters (the
  * clouds' key spaces nx*ny*nz laid end to end; 0 = the default 8 n_points + 2^20; < 0 is
- * rejected: the round-1 radix-sort path was removed in round 5). The same max_cells must be
+ * rejected: the round-1 radix-sort path was removed in round 5; key spaces too large for a
+ * histogram go through fgr_grid_subsample_sparse_* below). The same max_cells must be
  * passed to all three calls.
  * 1) fgr_grid_subsample_count: writes counts[c] (voxels of cloud c) and
  *    counts[n_clouds] (total) as int64; keeps the sorted state in `ws`. Dense path only:
@@ -92,6 +93,28 @@ int fgr_grid_subsample_count(const float* points, const int64_t* off, int32_t n_
 int fgr_grid_subsample_fill(int64_t n_points, int32_t n_clouds, int64_t max_cells, int64_t n_out,
                             void* ws, size_t ws_bytes, const float* points, float* out_points,
                             int64_t* out_keys, void* stream);
+
+/* Sparse path for large-extent clouds (outdoor lidar at a 5 cm voxel): the same outputs as
+ * the dense trio above, bit for bit, from one stable 8-bit radix sort of (voxel key, point
+ * index) over all points. The workspace (fgr_grid_subsample_sparse_workspace() bytes) and the
+ * time depend on n_points and n_clouds only, never on the clouds' extent; it needs no
+ * pre-clearing. `key_bits`: 0, or an upper bound on the bits of the clouds' summed key space
+ * (e.g. from the -(cells needed) a dense count reported) -- only ceil(key_bits / 8) sort passes
+ * are then launched (0: all eight; passes the key space does not need return at once).
+ * fgr_grid_subsample_sparse_count writes counts as fgr_grid_subsample_count does; a limit is
+ * reported, never truncated, as counts[n_clouds] < 0 with every counts[c] = 0:
+ *   -1  a cloud has more than 2^20 voxels along an axis,
+ *   -2  the clouds' summed key space nx*ny*nz reaches 2^62,
+ *   -3  key_bits is smaller than the summed key space needs.
+ * n_points >= 2^31 is an argument error. fgr_grid_subsample_sparse_fill must follow the count
+ * call on the same `ws`. */
+int fgr_grid_subsample_sparse_workspace(int64_t n_points, int32_t n_clouds, size_t* bytes);
+int fgr_grid_subsample_sparse_count(const float* points, const int64_t* off, int32_t n_clouds,
+                                    int64_t n_points, float dl, int32_t key_bits, void* ws,
+                                    size_t ws_bytes, int64_t* counts, void* stream);
+int fgr_grid_subsample_sparse_fill(int64_t n_points, int32_t n_clouds, int64_t n_out, void* ws,
+                                   size_t ws_bytes, const float* points, float* out_points,
+                                   int64_t* out_keys, void* stream);
 
 /* ---- radius neighbour search -----------------------------------------------------
  * Replaces batch_neighbors_kpconv_gpu (ball_query, finegrained_kpconv.py:266-293)

@@ -567,7 +567,8 @@ int fgr_lengths_to_offsets(const int64_t* lengths, int32_t n, int64_t* offsets, 
 /* ---- pose ----------------------------------------------------------------------------
  * fast_compute_rigid_transform (utils/se3_torch.py:226-273; threshold < 0 gives the
  * unthresholded compute_rigid_transform, :131-173) on n_batch independent problems
- * a, b (n_batch, n_pts, 3), w (n_batch, n_pts) -> out (n_batch, 3, 4). */
+ * a, b (n_batch, n_pts, 3), w (n_batch, n_pts) -> out (n_batch, 3, 4). A problem without a
+ * weight over the threshold gives R = I, t = 0 exactly (torch.svd of the zero covariance); a rank-1 covariance (collinear points) gives one of the optimal rotations. */
 int fgr_procrustes(const float* a, const float* b, const float* w, int64_t n_batch, int64_t n_pts,
                    float threshold, float* out, void* stream);
 
@@ -585,7 +586,9 @@ int fgr_pair_pose(const float* xyz, const float* corr, const float* logits, int6
  * on packed tensors (clouds src_0..src_{B-1}, tgt_0..tgt_{B-1}):
  *  fgr_overlap_pool     compute_overlaps, one level (finegrained_kpconv.py:560-569):
  *                       out[q] = clamp(mean_{h: idx[q,h] < n_prev} prev[idx[q,h]], 0, 1),
- *                       NaN for a row without valid entries (as the reference);
+ *                       NaN for a row without valid entries (as the reference); a negative
+ *                       index counts from the end (torch indexing), one below -n_prev is
+ *                       skipped;
  *  fgr_bce_logits_mean  nn.BCEWithLogitsLoss() on x[i * stride_x] vs y[i] (:264-267);
  *  fgr_transform_points se3_transform_list (se3_torch.py:70-90): rows of segment s get
  *                       pose[s] (3 x 4), or se3_inv(pose[s]) when inverse != 0;
@@ -594,7 +597,8 @@ int fgr_pair_pose(const float* xyz, const float* corr, const float* logits, int6
  *                       (columns of pair b: p_off[b]..p_off[b+1]): nearest positive by
  *                       torch.cdist's matrix-multiply distance (lowest index on ties),
  *                       row_mask = (its distance < r_p), points closer than r_n ignored,
- *                       row_loss = logsumexp - positive logit;
+ *                       row_loss = logsumexp - positive logit; a pair with no positive row
+ *                       gives row_loss NaN, row_mask 0;
  *  fgr_infonce_reduce   sum(loss[mask]) / sum(mask) per pair, mean over pairs (:295, 314);
  *  fgr_circle_loss      CircleLossFull.forward (feature_loss.py:160-243) with Euclidean feature
  *                       distances (feature_loss_type: circle, finegrained_regtr.py:86-88) over

@@ -12,13 +12,10 @@
 //   fgr_max_pool_bwd        max_pool (:125-141): the gradient goes to the row's first max entry
 //   fgr_corr_attention_bwd  CorrespondenceDecoder.simple_attention (finegrained_regtr.py:328-363)
 //                           backward: dq, dk of softmax(q.k scale) xyz
-//   fgr_segnorm_stats/_apply/_bwd
-//                           per-(segment, channel) normalisation with batch statistics: the
-//                           InstanceNorm of BatchNormBlock (:462-518, segment = cloud) and the
-//                           Res2Net BatchNorm1d in train() (res2net.py:126-159, one segment, affine)
 //   fgr_layernorm_bwd       nn.LayerNorm backward (transformers.py:105-107) + gamma / beta grads
 //   fgr_colsum              deterministic column sums (bias gradients)
-// (the MHA core backward, fgr_attention_bwd, is attention_bwd.hip)
+// (the MHA core backward, fgr_attention_bwd, is attention_bwd.hip; the training segment norm
+// has its own file too)
 //
 // Every reduction is deterministic: fixed-order partials (fp64 where they are long), merged in
 // order, and no floating-point atomics anywhere. The two scatters (KPConv, max-pool) run as
@@ -27,8 +24,6 @@
 #include "mfma.h"
 
 #include <algorithm>
-#include <cstdlib>
-#include <initializer_list>
 
 namespace fgr {
 namespace {
@@ -227,688 +222,6 @@ max_pool_bwd_csr_kernel(const int* __restrict__ start, const int* __restrict__ e
         if (am[qc] == h) acc += dy[qc];
     }
     dx[t] = acc;
-}
-
-// ---- per-(segment, channel) normalisation --------------------------------------------------
-// z = (v - mean) * rstd (* gamma + beta), v = x / row_div;  a = act(z);  y = post(a + residual)
-// Partial sums per (segment, chunk of kRowsChunk rows, channel), in fp64 and shifted by the
-// segment's first row (no cancellation for |mean| >> std), merged in chunk order.
-constexpr int kRowsChunk = 256;
-
-// The value of norm.hip's act_fn, tested in the other order. The two stay apart: the compiler
-// emits different (equivalent) code for the two orders, in either file's kernels.
-__device__ __forceinline__ float act_fwd(float z, int act) {
-    if (act == FGR_ACT_RELU) return fmaxf(z, 0.f);
-    if (act == FGR_ACT_LEAKY) return z > 0.f ? z : 0.1f * z;
-    return z;
-}
-// derivative factor from the activation's INPUT sign (torch: relu' = (out > 0), leaky' =
-// (in > 0 ? 1 : slope); out and in share their sign for both)
-__device__ __forceinline__ float act_grad(float zin, int act) {
-    if (act == FGR_ACT_RELU) return zin > 0.f ? 1.f : 0.f;
-    if (act == FGR_ACT_LEAKY) return zin > 0.f ? 1.f : 0.1f;
-    return 1.f;
-}
-
-struct SegArgs {
-    const float* x;
-    const float* row_div;
-    const int64_t* seg_off;
-    int n_seg;
-    int c;
-    int n_chunks;
-};
-
-__global__ void __launch_bounds__(256)
-segnorm_stats_kernel(SegArgs a, double* __restrict__ part) {
-    const int seg = blockIdx.y, chunk = blockIdx.x;
-    const int ch = blockIdx.z * 64 + threadIdx.x % 64;
-    const int rg = threadIdx.x / 64;
-    const int64_t b = a.seg_off[seg], e = a.seg_off[seg + 1];
-    const int64_t r0 = b + (int64_t)chunk * kRowsChunk;
-    double s1 = 0.0, s2 = 0.0;
-    int cnt = 0;
-    if (ch < a.c && r0 < e) {
-        const double piv = (double)(a.row_div ? a.x[b * a.c + ch] / a.row_div[b] : a.x[b * a.c + ch]);
-        const int64_t r1 = min(e, r0 + kRowsChunk);
-        for (int64_t r = r0 + rg; r < r1; r += 4) {
-            const float v = a.row_div ? a.x[r * a.c + ch] / a.row_div[r] : a.x[r * a.c + ch];
-            const double d = (double)v - piv;
-            s1 += d;
-            s2 += d * d;
-            ++cnt;
-        }
-    }
-    __shared__ double l1[4][64], l2[4][64];
-    __shared__ int lc[4][64];
-    l1[rg][threadIdx.x % 64] = s1;
-    l2[rg][threadIdx.x % 64] = s2;
-    lc[rg][threadIdx.x % 64] = cnt;
-    __syncthreads();
-    if (rg == 0 && ch < a.c) {
-        const int l = threadIdx.x;
-        s1 = ((l1[0][l] + l1[1][l]) + l1[2][l]) + l1[3][l];
-        s2 = ((l2[0][l] + l2[1][l]) + l2[2][l]) + l2[3][l];
-        cnt = lc[0][l] + lc[1][l] + lc[2][l] + lc[3][l];
-        double* p = part + (((int64_t)seg * a.n_chunks + chunk) * a.c + ch) * 3;
-        p[0] = s1;
-        p[1] = s2;
-        p[2] = (double)cnt;
-    }
-}
-
-// Thread per (segment, channel): merge the chunk partials in order -> mean, rstd, biased var.
-__global__ void __launch_bounds__(256)
-segnorm_merge_kernel(SegArgs a, const double* __restrict__ part, float eps, float* __restrict__ mean,
-                     float* __restrict__ rstd, float* __restrict__ var) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (int64_t)a.n_seg * a.c) return;
-    const int seg = (int)(t / a.c), ch = (int)(t % a.c);
-    const int64_t b = a.seg_off[seg], e = a.seg_off[seg + 1];
-    if (e <= b) {
-        mean[t] = 0.f; rstd[t] = 0.f; var[t] = 0.f;
-        return;
-    }
-    double s1 = 0.0, s2 = 0.0, n = 0.0;
-#pragma unroll 8
-    for (int k = 0; k < a.n_chunks; ++k) {                     // 8 chunk loads in flight
-        const double* p = part + (((int64_t)seg * a.n_chunks + k) * a.c + ch) * 3;
-        s1 += p[0];
-        s2 += p[1];
-        n += p[2];
-    }
-    const double piv = (double)(a.row_div ? a.x[b * a.c + ch] / a.row_div[b] : a.x[b * a.c + ch]);
-    const double m1 = s1 / n;
-    const double vv = fmax(s2 / n - m1 * m1, 0.0);
-    mean[t] = (float)(piv + m1);
-    var[t] = (float)vv;
-    rstd[t] = (float)(1.0 / sqrt(vv + (double)eps));
-}
-
-struct SegApply {
-    SegArgs a;
-    int64_t n;
-    const float* mean;
-    const float* rstd;
-    const float* gamma;
-    const float* beta;
-    int act;
-    const float* residual;
-    int post_act;
-};
-
-__global__ void __launch_bounds__(256)
-segnorm_apply_kernel(SegApply p, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= p.n * p.a.c) return;
-    const int64_t r = t / p.a.c;
-    const int ch = (int)(t - r * p.a.c);
-    const int seg = find_segment(p.a.seg_off, p.a.n_seg, r);
-    const float v = p.a.row_div ? p.a.x[t] / p.a.row_div[r] : p.a.x[t];
-    const int64_t sc = (int64_t)seg * p.a.c + ch;
-    float z = (v - p.mean[sc]) * p.rstd[sc];
-    if (p.gamma) z = z * p.gamma[ch] + p.beta[ch];
-    float y = act_fwd(z, p.act);
-    if (p.residual) y = act_fwd(y + p.residual[t], p.post_act);
-    out[t] = y;
-}
-
-// dz = dy * post'(y) * act'(z); partial sums of dz and dz * xhat per (segment, chunk, channel)
-__global__ void __launch_bounds__(256)
-segnorm_bwd_stats_kernel(SegApply p, const float* __restrict__ dy, const float* __restrict__ y,
-                         double* __restrict__ part) {
-    const int seg = blockIdx.y, chunk = blockIdx.x;
-    const int ch = blockIdx.z * 64 + threadIdx.x % 64;
-    const int rg = threadIdx.x / 64;
-    const int C = p.a.c;
-    const int64_t b = p.a.seg_off[seg], e = p.a.seg_off[seg + 1];
-    const int64_t r0 = b + (int64_t)chunk * kRowsChunk;
-    double s1 = 0.0, s2 = 0.0;
-    if (ch < C && r0 < e) {
-        const int64_t sc = (int64_t)seg * C + ch;
-        const float mu = p.mean[sc], rs = p.rstd[sc];
-        const float g = p.gamma ? p.gamma[ch] : 1.f, bt = p.gamma ? p.beta[ch] : 0.f;
-        const int64_t r1 = min(e, r0 + kRowsChunk);
-        for (int64_t r = r0 + rg; r < r1; r += 4) {
-            const int64_t t = r * C + ch;
-            const float v = p.a.row_div ? p.a.x[t] / p.a.row_div[r] : p.a.x[t];
-            const float xh = (v - mu) * rs;
-            float gr = dy[t];
-            if (p.residual) gr *= act_grad(y[t], p.post_act);
-            const float dz = gr * act_grad(xh * g + bt, p.act);
-            s1 += (double)dz;
-            s2 += (double)dz * (double)xh;
-        }
-    }
-    __shared__ double l1[4][64], l2[4][64];
-    l1[rg][threadIdx.x % 64] = s1;
-    l2[rg][threadIdx.x % 64] = s2;
-    __syncthreads();
-    if (rg == 0 && ch < C) {
-        const int l = threadIdx.x;
-        double* q = part + (((int64_t)seg * p.a.n_chunks + chunk) * C + ch) * 2;
-        q[0] = ((l1[0][l] + l1[1][l]) + l1[2][l]) + l1[3][l];
-        q[1] = ((l2[0][l] + l2[1][l]) + l2[2][l]) + l2[3][l];
-    }
-}
-
-// Thread per (segment, channel): the chunk sums in order -> sdz, sdzx (per segment); with
-// gamma, thread per channel also sums over segments -> dgamma = sum dz xhat, dbeta = sum dz.
-__global__ void __launch_bounds__(256)
-segnorm_bwd_merge_kernel(SegArgs a, const double* __restrict__ part, float* __restrict__ sums,
-                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (int64_t)a.n_seg * a.c) return;
-    const int seg = (int)(t / a.c), ch = (int)(t % a.c);
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll 8
-    for (int k = 0; k < a.n_chunks; ++k) {
-        const double* p = part + (((int64_t)seg * a.n_chunks + k) * a.c + ch) * 2;
-        s1 += p[0];
-        s2 += p[1];
-    }
-    sums[2 * t] = (float)s1;
-    sums[2 * t + 1] = (float)s2;
-    if (dgamma && seg == 0) {
-        double g1 = 0.0, g2 = 0.0;
-        for (int sg = 0; sg < a.n_seg; ++sg)
-#pragma unroll 8
-            for (int k = 0; k < a.n_chunks; ++k) {
-                const double* p = part + (((int64_t)sg * a.n_chunks + k) * a.c + ch) * 2;
-                g1 += p[0];
-                g2 += p[1];
-            }
-        dbeta[ch] = (float)g1;
-        dgamma[ch] = (float)g2;
-    }
-}
-
-// dx = rstd * gamma * (dz - mean(dz) - xhat * mean(dz xhat)) / row_div; dres = dy * post'(y)
-__global__ void __launch_bounds__(256)
-segnorm_bwd_apply_kernel(SegApply p, const float* __restrict__ dy, const float* __restrict__ y,
-                         const float* __restrict__ sums, float* __restrict__ dx,
-                         float* __restrict__ dres) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int C = p.a.c;
-    if (t >= p.n * C) return;
-    const int64_t r = t / C;
-    const int ch = (int)(t - r * C);
-    const int seg = find_segment(p.a.seg_off, p.a.n_seg, r);
-    const int64_t sc = (int64_t)seg * C + ch;
-    const float inv_n = 1.0f / (float)(p.a.seg_off[seg + 1] - p.a.seg_off[seg]);
-    const float mu = p.mean[sc], rs = p.rstd[sc];
-    const float g = p.gamma ? p.gamma[ch] : 1.f, bt = p.gamma ? p.beta[ch] : 0.f;
-    const float rd = p.a.row_div ? p.a.row_div[r] : 1.f;
-    const float v = p.a.x[t] / rd;
-    const float xh = (v - mu) * rs;
-    float gr = dy[t];
-    if (p.residual) gr *= act_grad(y[t], p.post_act);
-    if (dres) dres[t] = gr;
-    const float dz = gr * act_grad(xh * g + bt, p.act);
-    const float m1 = sums[2 * sc] * inv_n, m2 = sums[2 * sc + 1] * inv_n;
-    dx[t] = rs * g * (dz - m1 - xh * m2) / rd;
-}
-
-// ---- the same four kernels on 16-B rows (c % 4 == 0, aligned): one float4 of channels per
-// thread, four rows in flight per thread in the statistics (the scalar kernels above kept one
-// dependent load per row and channel: 22 / 38 us per ModelNet call), 32-bit element indices
-// and the segment table in LDS for the elementwise passes. Same partial layout and chunking,
-// so the merges are shared.
-constexpr int kSegLds = 64;        // segment tables up to this many segments cached in LDS
-
-__device__ __forceinline__ int seg_of_row(const int64_t* so_lds, const int64_t* so, int n_seg, int64_t r) {
-    return n_seg <= kSegLds ? find_segment(so_lds, n_seg, r) : find_segment(so, n_seg, r);
-}
-
-__global__ void __launch_bounds__(256)
-segnorm_stats4_kernel(SegArgs a, double* __restrict__ part) {
-    const int seg = blockIdx.y, chunk = blockIdx.x;
-    const int qd = threadIdx.x & 15, rg = threadIdx.x >> 4;          // 16 quads x 16 row groups
-    const int ch = blockIdx.z * 64 + 4 * qd;
-    const int C = a.c;
-    const int64_t b = a.seg_off[seg], e = a.seg_off[seg + 1];
-    const int64_t r0 = b + (int64_t)chunk * kRowsChunk;
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    int cnt = 0;
-    if (ch < C && r0 < e) {
-        const float4 pv = ld4(a.x + b * C + ch);
-        const float pd = a.row_div ? a.row_div[b] : 1.f;
-        const double piv[4] = {(double)(a.row_div ? pv.x / pd : pv.x), (double)(a.row_div ? pv.y / pd : pv.y),
-                               (double)(a.row_div ? pv.z / pd : pv.z), (double)(a.row_div ? pv.w / pd : pv.w)};
-        const int64_t r1 = min(e, r0 + kRowsChunk);
-        for (int64_t r = r0 + rg; r < r1; r += 64) {
-            float4 v[4];
-            float rd[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t rr = min(r + 16 * u, r1 - 1);
-                v[u] = ld4(a.x + rr * C + ch);
-                rd[u] = a.row_div ? a.row_div[rr] : 1.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (r + 16 * u >= r1) break;
-                const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float f = a.row_div ? vv[j] / rd[u] : vv[j];
-                    const double d = (double)f - piv[j];
-                    s1[j] += d;
-                    s2[j] += d * d;
-                }
-                ++cnt;
-            }
-        }
-    }
-    __shared__ double l1[16][64], l2[16][64];
-    __shared__ int lc[16][16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        l1[rg][4 * qd + j] = s1[j];
-        l2[rg][4 * qd + j] = s2[j];
-    }
-    lc[rg][qd] = cnt;
-    __syncthreads();
-    const int l = threadIdx.x;
-    if (l < 64 && blockIdx.z * 64 + l < C) {
-        double t1 = 0.0, t2 = 0.0;
-        int tc = 0;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            t1 += l1[g][l];
-            t2 += l2[g][l];
-            tc += lc[g][l >> 2];
-        }
-        double* p = part + (((int64_t)seg * a.n_chunks + chunk) * C + blockIdx.z * 64 + l) * 3;
-        p[0] = t1;
-        p[1] = t2;
-        p[2] = (double)tc;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-segnorm_apply4_kernel(SegApply p, float* __restrict__ out) {
-    __shared__ int64_t so[kSegLds + 1];
-    if (p.a.n_seg <= kSegLds)
-        for (int i = threadIdx.x; i <= p.a.n_seg; i += 256) so[i] = p.a.seg_off[i];
-    __syncthreads();
-    const int c4 = p.a.c >> 2;
-    const int t = blockIdx.x * 256 + threadIdx.x;                  // float4 index (< 2^31)
-    if (t >= (int)(p.n * c4)) return;
-    const int r = t / c4;
-    const int ch = 4 * (t - r * c4);
-    const int seg = seg_of_row(so, p.a.seg_off, p.a.n_seg, r);
-    const int64_t sc = (int64_t)seg * p.a.c + ch;
-    const float4 xv = ld4(p.a.x + 4 * (int64_t)t);
-    const float rd = p.a.row_div ? p.a.row_div[r] : 1.f;
-    const float4 mu = ld4(p.mean + sc), rs = ld4(p.rstd + sc);
-    float4 gm = make_float4(1.f, 1.f, 1.f, 1.f), bt = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.gamma) {
-        gm = ld4(p.gamma + ch);
-        bt = ld4(p.beta + ch);
-    }
-    float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.residual) rv = ld4(p.residual + 4 * (int64_t)t);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ms[4] = {mu.x, mu.y, mu.z, mu.w};
-    const float ss[4] = {rs.x, rs.y, rs.z, rs.w}, gs[4] = {gm.x, gm.y, gm.z, gm.w};
-    const float bs[4] = {bt.x, bt.y, bt.z, bt.w}, res[4] = {rv.x, rv.y, rv.z, rv.w};
-    float y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float v = p.a.row_div ? xs[j] / rd : xs[j];
-        float z = (v - ms[j]) * ss[j];
-        if (p.gamma) z = z * gs[j] + bs[j];
-        y[j] = act_fwd(z, p.act);
-        if (p.residual) y[j] = act_fwd(y[j] + res[j], p.post_act);
-    }
-    *reinterpret_cast<float4*>(out + 4 * (int64_t)t) = make_float4(y[0], y[1], y[2], y[3]);
-}
-
-__global__ void __launch_bounds__(256)
-segnorm_bwd_stats4_kernel(SegApply p, const float* __restrict__ dy, const float* __restrict__ y,
-                          double* __restrict__ part) {
-    const int seg = blockIdx.y, chunk = blockIdx.x;
-    const int qd = threadIdx.x & 15, rg = threadIdx.x >> 4;
-    const int ch = blockIdx.z * 64 + 4 * qd;
-    const int C = p.a.c;
-    const int64_t b = p.a.seg_off[seg], e = p.a.seg_off[seg + 1];
-    const int64_t r0 = b + (int64_t)chunk * kRowsChunk;
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    if (ch < C && r0 < e) {
-        const int64_t sc = (int64_t)seg * C + ch;
-        const float4 mu4 = ld4(p.mean + sc), rs4 = ld4(p.rstd + sc);
-        float4 g4 = make_float4(1.f, 1.f, 1.f, 1.f), b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p.gamma) {
-            g4 = ld4(p.gamma + ch);
-            b4 = ld4(p.beta + ch);
-        }
-        const float mu[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, rs[4] = {rs4.x, rs4.y, rs4.z, rs4.w};
-        const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-        const int64_t r1 = min(e, r0 + kRowsChunk);
-        for (int64_t r = r0 + rg; r < r1; r += 64) {
-            float4 xv[4], dv[4], yv[4];
-            float rd[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t rr = min(r + 16 * u, r1 - 1);
-                const int64_t o = rr * C + ch;
-                xv[u] = ld4(p.a.x + o);
-                dv[u] = ld4(dy + o);
-                yv[u] = p.residual ? ld4(y + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-                rd[u] = p.a.row_div ? p.a.row_div[rr] : 1.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (r + 16 * u >= r1) break;
-                const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
-                const float ds[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
-                const float ys[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = p.a.row_div ? xs[j] / rd[u] : xs[j];
-                    const float xh = (v - mu[j]) * rs[j];
-                    float gr = ds[j];
-                    if (p.residual) gr *= act_grad(ys[j], p.post_act);
-                    const float dz = gr * act_grad(xh * gg[j] + bb[j], p.act);
-                    s1[j] += (double)dz;
-                    s2[j] += (double)dz * (double)xh;
-                }
-            }
-        }
-    }
-    __shared__ double l1[16][64], l2[16][64];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        l1[rg][4 * qd + j] = s1[j];
-        l2[rg][4 * qd + j] = s2[j];
-    }
-    __syncthreads();
-    const int l = threadIdx.x;
-    if (l < 64 && blockIdx.z * 64 + l < C) {
-        double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            t1 += l1[g][l];
-            t2 += l2[g][l];
-        }
-        double* q = part + (((int64_t)seg * p.a.n_chunks + chunk) * C + blockIdx.z * 64 + l) * 2;
-        q[0] = t1;
-        q[1] = t2;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-segnorm_bwd_apply4_kernel(SegApply p, const float* __restrict__ dy, const float* __restrict__ y,
-                          const float* __restrict__ sums, float* __restrict__ dx,
-                          float* __restrict__ dres) {
-    __shared__ int64_t so[kSegLds + 1];
-    if (p.a.n_seg <= kSegLds)
-        for (int i = threadIdx.x; i <= p.a.n_seg; i += 256) so[i] = p.a.seg_off[i];
-    __syncthreads();
-    const int C = p.a.c, c4 = C >> 2;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= (int)(p.n * c4)) return;
-    const int r = t / c4;
-    const int ch = 4 * (t - r * c4);
-    const int seg = seg_of_row(so, p.a.seg_off, p.a.n_seg, r);
-    const int64_t sc = (int64_t)seg * C + ch;
-    const int64_t o = 4 * (int64_t)t;
-    const float inv_n = 1.0f / (float)(p.a.seg_off[seg + 1] - p.a.seg_off[seg]);
-    const float4 mu4 = ld4(p.mean + sc), rs4 = ld4(p.rstd + sc);
-    float4 g4 = make_float4(1.f, 1.f, 1.f, 1.f), b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.gamma) {
-        g4 = ld4(p.gamma + ch);
-        b4 = ld4(p.beta + ch);
-    }
-    const float rd = p.a.row_div ? p.a.row_div[r] : 1.f;
-    const float4 xv = ld4(p.a.x + o), dv = ld4(dy + o);
-    const float4 yv = p.residual ? ld4(y + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 sa = ld4(sums + 2 * sc), sb = ld4(sums + 2 * sc + 4);   // (s1, s2) per channel
-    const float mu[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, rs[4] = {rs4.x, rs4.y, rs4.z, rs4.w};
-    const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w};
-    const float ys[4] = {yv.x, yv.y, yv.z, yv.w};
-    const float m1s[4] = {sa.x, sa.z, sb.x, sb.z}, m2s[4] = {sa.y, sa.w, sb.y, sb.w};
-    float gx[4], gres[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float v = xs[j] / rd;
-        const float xh = (v - mu[j]) * rs[j];
-        float gr = ds[j];
-        if (p.residual) gr *= act_grad(ys[j], p.post_act);
-        gres[j] = gr;
-        const float dz = gr * act_grad(xh * gg[j] + bb[j], p.act);
-        const float m1 = m1s[j] * inv_n, m2 = m2s[j] * inv_n;
-        gx[j] = rs[j] * gg[j] * (dz - m1 - xh * m2) / rd;
-    }
-    if (dres) *reinterpret_cast<float4*>(dres + o) = make_float4(gres[0], gres[1], gres[2], gres[3]);
-    *reinterpret_cast<float4*>(dx + o) = make_float4(gx[0], gx[1], gx[2], gx[3]);
-}
-
-// ---- the merges folded into the apply passes (segments of at most kSegFuseChunks chunks, e.g.
-// ModelNet's per-cloud InstanceNorms): one block per (chunk, segment, 64 channels) as the
-// statistics pass, whose first 64 threads merge the 64 channels' chunk partials exactly as the
-// merge kernels do (same order, same roundings: bit-identical results) into LDS, then the block
-// applies them to its chunk's rows. The chunk-0 block writes mean / rstd / var (forward) or
-// dgamma / dbeta (backward, segment 0). One launch per norm and direction instead of two.
-constexpr int kSegFuseChunks = 16;          // up to here the merge order of the merge kernels
-constexpr int kSegFuseChunksMax = 64;       // beyond: the separate merge kernels
-
-__global__ void __launch_bounds__(256)
-segnorm_merge_apply4_kernel(SegApply p, const double* __restrict__ part, float eps, float* __restrict__ mean,
-                            float* __restrict__ rstd, float* __restrict__ var, float* __restrict__ out) {
-    __shared__ float smu[64], srs[64];
-    __shared__ double sred[3][3][64];
-    const int seg = blockIdx.y, chunk = blockIdx.x;
-    const int C = p.a.c;
-    const int64_t b = p.a.seg_off[seg], e = p.a.seg_off[seg + 1];
-    const int64_t r0 = b + (int64_t)chunk * kRowsChunk;
-    if (r0 >= e && chunk != 0) return;                         // block-uniform
-    const int tid = threadIdx.x;
-    // more than kSegFuseChunks chunks (the BatchNorms over every row): the four waves sum the
-    // chunks congruent to their index mod 4, combined in wave order
-    const bool split4 = p.a.n_chunks > kSegFuseChunks;
-    if (split4 && tid >= 64 && blockIdx.z * 64 + (tid & 63) < C) {
-        const int ch = blockIdx.z * 64 + (tid & 63), w = tid >> 6;
-        double s1 = 0.0, s2 = 0.0, n = 0.0;
-#pragma unroll 4
-        for (int k = w; k < p.a.n_chunks; k += 4) {
-            const double* q = part + (((int64_t)seg * p.a.n_chunks + k) * C + ch) * 3;
-            s1 += q[0];
-            s2 += q[1];
-            n += q[2];
-        }
-        sred[w - 1][0][tid & 63] = s1;
-        sred[w - 1][1][tid & 63] = s2;
-        sred[w - 1][2][tid & 63] = n;
-    }
-    if (split4) __syncthreads();
-    if (tid < 64 && blockIdx.z * 64 + tid < C) {
-        const int ch = blockIdx.z * 64 + tid;
-        const int64_t t = (int64_t)seg * C + ch;
-        float mu = 0.f, rs = 0.f, vr = 0.f;
-        if (e > b) {
-            double s1 = 0.0, s2 = 0.0, n = 0.0;
-#pragma unroll 8
-            for (int k = 0; k < p.a.n_chunks; k += split4 ? 4 : 1) {
-                const double* q = part + (((int64_t)seg * p.a.n_chunks + k) * C + ch) * 3;
-                s1 += q[0];
-                s2 += q[1];
-                n += q[2];
-            }
-            if (split4)
-                for (int w = 0; w < 3; ++w) {
-                    s1 += sred[w][0][tid];
-                    s2 += sred[w][1][tid];
-                    n += sred[w][2][tid];
-                }
-            const double piv = (double)(p.a.row_div ? p.a.x[b * C + ch] / p.a.row_div[b] : p.a.x[b * C + ch]);
-            const double m1 = s1 / n;
-            const double vv = fmax(s2 / n - m1 * m1, 0.0);
-            mu = (float)(piv + m1);
-            vr = (float)vv;
-            rs = (float)(1.0 / sqrt(vv + (double)eps));
-        }
-        smu[tid] = mu;
-        srs[tid] = rs;
-        if (chunk == 0) {
-            mean[t] = mu;
-            rstd[t] = rs;
-            var[t] = vr;
-        }
-    }
-    __syncthreads();
-    if (r0 >= e) return;
-    const int qd = tid & 15, rg = tid >> 4;
-    const int ch = blockIdx.z * 64 + 4 * qd;
-    if (ch >= C) return;
-    const float ms[4] = {smu[4 * qd], smu[4 * qd + 1], smu[4 * qd + 2], smu[4 * qd + 3]};
-    const float ss[4] = {srs[4 * qd], srs[4 * qd + 1], srs[4 * qd + 2], srs[4 * qd + 3]};
-    float4 gm = make_float4(1.f, 1.f, 1.f, 1.f), bt = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.gamma) {
-        gm = ld4(p.gamma + ch);
-        bt = ld4(p.beta + ch);
-    }
-    const float gs[4] = {gm.x, gm.y, gm.z, gm.w}, bs[4] = {bt.x, bt.y, bt.z, bt.w};
-    const int64_t r1 = min(e, r0 + kRowsChunk);
-    for (int64_t r = r0 + rg; r < r1; r += 64) {
-        float4 xv[4], rv[4];
-        float rd[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t rr = min(r + 16 * u, r1 - 1);
-            xv[u] = ld4(p.a.x + rr * C + ch);
-            rd[u] = p.a.row_div ? p.a.row_div[rr] : 1.f;
-            rv[u] = p.residual ? ld4(p.residual + rr * C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (r + 16 * u >= r1) break;
-            const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
-            const float res[4] = {rv[u].x, rv[u].y, rv[u].z, rv[u].w};
-            float y[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float v = p.a.row_div ? xs[j] / rd[u] : xs[j];
-                float z = (v - ms[j]) * ss[j];
-                if (p.gamma) z = z * gs[j] + bs[j];
-                y[j] = act_fwd(z, p.act);
-                if (p.residual) y[j] = act_fwd(y[j] + res[j], p.post_act);
-            }
-            *reinterpret_cast<float4*>(out + (r + 16 * u) * C + ch) = make_float4(y[0], y[1], y[2], y[3]);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256)
-segnorm_bwd_merge_apply4_kernel(SegApply p, const float* __restrict__ dy, const float* __restrict__ y,
-                                const double* __restrict__ part, float* __restrict__ dgamma,
-                                float* __restrict__ dbeta, float* __restrict__ dx, float* __restrict__ dres) {
-    __shared__ float sm1[64], sm2[64];
-    __shared__ double sred[3][2][64];
-    const int seg = blockIdx.y, chunk = blockIdx.x;
-    const int C = p.a.c;
-    const int64_t b = p.a.seg_off[seg], e = p.a.seg_off[seg + 1];
-    const int64_t r0 = b + (int64_t)chunk * kRowsChunk;
-    const bool gblock = dgamma && seg == 0 && chunk == 0;
-    if (r0 >= e && !gblock) return;                            // block-uniform
-    const int tid = threadIdx.x;
-    const bool split4 = p.a.n_chunks > kSegFuseChunks;         // as the forward
-    if (split4 && tid >= 64 && blockIdx.z * 64 + (tid & 63) < C) {
-        const int ch = blockIdx.z * 64 + (tid & 63), w = tid >> 6;
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-        for (int k = w; k < p.a.n_chunks; k += 4) {
-            const double* q = part + (((int64_t)seg * p.a.n_chunks + k) * C + ch) * 2;
-            s1 += q[0];
-            s2 += q[1];
-        }
-        sred[w - 1][0][tid & 63] = s1;
-        sred[w - 1][1][tid & 63] = s2;
-    }
-    if (split4) __syncthreads();
-    if (tid < 64 && blockIdx.z * 64 + tid < C) {
-        const int ch = blockIdx.z * 64 + tid;
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll 8
-        for (int k = 0; k < p.a.n_chunks; k += split4 ? 4 : 1) {
-            const double* q = part + (((int64_t)seg * p.a.n_chunks + k) * C + ch) * 2;
-            s1 += q[0];
-            s2 += q[1];
-        }
-        if (split4)
-            for (int w = 0; w < 3; ++w) {
-                s1 += sred[w][0][tid];
-                s2 += sred[w][1][tid];
-            }
-        sm1[tid] = (float)s1;
-        sm2[tid] = (float)s2;
-        if (gblock) {
-            double g1 = 0.0, g2 = 0.0;
-            for (int sg = 0; sg < p.a.n_seg; ++sg)
-#pragma unroll 8
-                for (int k = 0; k < p.a.n_chunks; ++k) {
-                    const double* q = part + (((int64_t)sg * p.a.n_chunks + k) * C + ch) * 2;
-                    g1 += q[0];
-                    g2 += q[1];
-                }
-            dbeta[ch] = (float)g1;
-            dgamma[ch] = (float)g2;
-        }
-    }
-    __syncthreads();
-    if (r0 >= e) return;
-    const int qd = tid & 15, rg = tid >> 4;
-    const int ch = blockIdx.z * 64 + 4 * qd;
-    if (ch >= C) return;
-    const int64_t sc = (int64_t)seg * C + ch;
-    const float inv_n = 1.0f / (float)(e - b);
-    const float4 mu4 = ld4(p.mean + sc), rs4 = ld4(p.rstd + sc);
-    float4 g4 = make_float4(1.f, 1.f, 1.f, 1.f), b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.gamma) {
-        g4 = ld4(p.gamma + ch);
-        b4 = ld4(p.beta + ch);
-    }
-    const float mu[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, rs[4] = {rs4.x, rs4.y, rs4.z, rs4.w};
-    const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-    const float m1s[4] = {sm1[4 * qd], sm1[4 * qd + 1], sm1[4 * qd + 2], sm1[4 * qd + 3]};
-    const float m2s[4] = {sm2[4 * qd], sm2[4 * qd + 1], sm2[4 * qd + 2], sm2[4 * qd + 3]};
-    const int64_t r1 = min(e, r0 + kRowsChunk);
-    for (int64_t r = r0 + rg; r < r1; r += 64) {
-        float4 xv[4], dv[4], yv[4];
-        float rdv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t rr = min(r + 16 * u, r1 - 1);
-            const int64_t o = rr * C + ch;
-            xv[u] = ld4(p.a.x + o);
-            dv[u] = ld4(dy + o);
-            yv[u] = p.residual ? ld4(y + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-            rdv[u] = p.a.row_div ? p.a.row_div[rr] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (r + 16 * u >= r1) break;
-            const int64_t o = (r + 16 * u) * C + ch;
-            const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, ds[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
-            const float ys[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
-            const float rd = rdv[u];
-            float gx[4], gres[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float v = xs[j] / rd;
-                const float xh = (v - mu[j]) * rs[j];
-                float gr = ds[j];
-                if (p.residual) gr *= act_grad(ys[j], p.post_act);
-                gres[j] = gr;
-                const float dz = gr * act_grad(xh * gg[j] + bb[j], p.act);
-                const float m1 = m1s[j] * inv_n, m2 = m2s[j] * inv_n;
-                gx[j] = rs[j] * gg[j] * (dz - m1 - xh * m2) / rd;
-            }
-            if (dres) *reinterpret_cast<float4*>(dres + o) = make_float4(gres[0], gres[1], gres[2], gres[3]);
-            *reinterpret_cast<float4*>(dx + o) = make_float4(gx[0], gx[1], gx[2], gx[3]);
-        }
-    }
 }
 
 // ---- LayerNorm backward ------------------------------------------------------------------
@@ -1365,151 +678,6 @@ extern "C" int fgr_corr_attention_bwd(const float* q, int64_t ld_q, const float*
 #undef CAB
     }
     FGR_CHECK_LAUNCH("corr_attn_bwd_dk_kernel");
-    return FGR_OK;
-}
-
-// the float4 segment-norm kernels: c % 4 == 0, every given pointer 16-B aligned (NULL
-// allowed), float4 indices below 2^31
-static bool seg_vec_ok(int64_t n, int c, std::initializer_list<const void*> ptrs) {
-    if (c % 4 != 0 || n * c / 4 >= (int64_t)1 << 31) return false;
-    for (const void* q : ptrs)
-        if (reinterpret_cast<uintptr_t>(q) & 15) return false;
-    return true;
-}
-
-static int seg_chunks(int64_t max_seg_len) { return (int)std::max<int64_t>(1, ceil_div(max_seg_len, kRowsChunk)); }
-
-extern "C" int fgr_segnorm_workspace(int64_t max_seg_len, int32_t c, int32_t n_seg, size_t* bytes) {
-    FGR_REQUIRE(bytes && max_seg_len >= 0 && c > 0 && n_seg >= 0, "fgr_segnorm_workspace: bad arguments");
-    *bytes = (size_t)n_seg * seg_chunks(max_seg_len) * c * 3 * sizeof(double);
-    return FGR_OK;
-}
-
-extern "C" int fgr_segnorm_stats(const float* x, int64_t n, int32_t c, const int64_t* seg_off,
-                                 int32_t n_seg, int64_t max_seg_len, const float* row_div, float eps,
-                                 float* mean, float* rstd, float* var, void* ws, size_t ws_bytes,
-                                 void* stream) {
-    FGR_REQUIRE(n >= 0 && c > 0 && n_seg > 0 && max_seg_len >= 0, "fgr_segnorm_stats: bad arguments");
-    FGR_REQUIRE(x && seg_off && mean && rstd && var && ws, "fgr_segnorm_stats: null pointer");
-    size_t need = 0;
-    fgr_segnorm_workspace(max_seg_len, c, n_seg, &need);
-    FGR_REQUIRE(ws_bytes >= need, "fgr_segnorm_stats: workspace too small");
-    SegArgs a{x, row_div, seg_off, n_seg, c, seg_chunks(max_seg_len)};
-    hipStream_t st = as_stream(stream);
-    if (seg_vec_ok(n, c, {x}))
-        hipLaunchKernelGGL(segnorm_stats4_kernel, dim3(a.n_chunks, n_seg, (unsigned)ceil_div(c, 64)),
-                           dim3(256), 0, st, a, (double*)ws);
-    else
-        hipLaunchKernelGGL(segnorm_stats_kernel, dim3(a.n_chunks, n_seg, (unsigned)ceil_div(c, 64)),
-                           dim3(256), 0, st, a, (double*)ws);
-    FGR_CHECK_LAUNCH("segnorm_stats_kernel");
-    hipLaunchKernelGGL(segnorm_merge_kernel, dim3((unsigned)ceil_div((int64_t)n_seg * c, 256)), dim3(256),
-                       0, st, a, (const double*)ws, eps, mean, rstd, var);
-    FGR_CHECK_LAUNCH("segnorm_merge_kernel");
-    return FGR_OK;
-}
-
-extern "C" int fgr_segnorm_apply(const float* x, int64_t n, int32_t c, const int64_t* seg_off,
-                                 int32_t n_seg, const float* row_div, const float* mean,
-                                 const float* rstd, const float* gamma, const float* beta, int32_t act,
-                                 const float* residual, int32_t post_act, float* out, void* stream) {
-    FGR_REQUIRE(n >= 0 && c > 0 && n_seg > 0 && (!gamma == !beta), "fgr_segnorm_apply: bad arguments");
-    if (n == 0) return FGR_OK;
-    FGR_REQUIRE(x && seg_off && mean && rstd && out, "fgr_segnorm_apply: null pointer");
-    SegApply p{{x, row_div, seg_off, n_seg, c, 1}, n, mean, rstd, gamma, beta, act, residual, post_act};
-    if (seg_vec_ok(n, c, {x, out, residual, mean, rstd, gamma, beta}))
-        hipLaunchKernelGGL(segnorm_apply4_kernel, dim3((unsigned)ceil_div(n * c / 4, 256)), dim3(256), 0,
-                           as_stream(stream), p, out);
-    else
-        hipLaunchKernelGGL(segnorm_apply_kernel, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0,
-                           as_stream(stream), p, out);
-    FGR_CHECK_LAUNCH("segnorm_apply_kernel");
-    return FGR_OK;
-}
-
-extern "C" int fgr_segnorm_fwd(const float* x, int64_t n, int32_t c, const int64_t* seg_off,
-                               int32_t n_seg, int64_t max_seg_len, const float* row_div, float eps,
-                               float* mean, float* rstd, float* var, const float* gamma,
-                               const float* beta, int32_t act, const float* residual,
-                               int32_t post_act, float* out, void* ws, size_t ws_bytes,
-                               void* stream) {
-    static const bool fuse = [] { const char* e = getenv("FGR_SEG_FUSED"); return !(e && e[0] == '0'); }();
-    if (fuse && n > 0 && c > 0 && n_seg > 0 && max_seg_len > 0 && seg_chunks(max_seg_len) <= kSegFuseChunksMax &&
-        x && seg_off && mean && rstd && var && out && ws &&
-        seg_vec_ok(n, c, {x, out, residual, mean, rstd, gamma, beta}) && (!gamma == !beta)) {
-        size_t need = 0;
-        fgr_segnorm_workspace(max_seg_len, c, n_seg, &need);
-        FGR_REQUIRE(ws_bytes >= need, "fgr_segnorm_fwd: workspace too small");
-        SegApply p{{x, row_div, seg_off, n_seg, c, seg_chunks(max_seg_len)}, n, mean, rstd, gamma, beta, act,
-                   residual, post_act};
-        hipStream_t st = as_stream(stream);
-        const dim3 grid(p.a.n_chunks, n_seg, (unsigned)ceil_div(c, 64));
-        hipLaunchKernelGGL(segnorm_stats4_kernel, grid, dim3(256), 0, st, p.a, (double*)ws);
-        FGR_CHECK_LAUNCH("segnorm_stats4_kernel");
-        hipLaunchKernelGGL(segnorm_merge_apply4_kernel, grid, dim3(256), 0, st, p, (const double*)ws, eps,
-                           mean, rstd, var, out);
-        FGR_CHECK_LAUNCH("segnorm_merge_apply4_kernel");
-        return FGR_OK;
-    }
-    const int rc = fgr_segnorm_stats(x, n, c, seg_off, n_seg, max_seg_len, row_div, eps, mean, rstd,
-                                     var, ws, ws_bytes, stream);
-    if (rc != FGR_OK) return rc;
-    return fgr_segnorm_apply(x, n, c, seg_off, n_seg, row_div, mean, rstd, gamma, beta, act, residual,
-                             post_act, out, stream);
-}
-
-extern "C" int fgr_segnorm_bwd(const float* x, int64_t n, int32_t c, const int64_t* seg_off,
-                               int32_t n_seg, int64_t max_seg_len, const float* row_div,
-                               const float* mean, const float* rstd, const float* gamma,
-                               const float* beta, int32_t act, int32_t has_residual, int32_t post_act,
-                               const float* y, const float* dy, float* dx, float* dres,
-                               float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
-    FGR_REQUIRE(n >= 0 && c > 0 && n_seg > 0 && (!gamma == !beta) && (!gamma == !dgamma) &&
-                    (!dgamma == !dbeta), "fgr_segnorm_bwd: bad arguments");
-    FGR_REQUIRE(x && seg_off && mean && rstd && dy && dx && ws && (!has_residual || y),
-                "fgr_segnorm_bwd: null pointer");
-    // workspace: the chunk partials (2 doubles per entry, inside the stats' 3-double region of
-    // fgr_segnorm_workspace bytes) followed by the merged sums (2 floats per (segment, channel))
-    size_t part_bytes = 0;
-    fgr_segnorm_workspace(max_seg_len, c, n_seg, &part_bytes);
-    FGR_REQUIRE(ws_bytes >= part_bytes + (size_t)n_seg * c * 2 * sizeof(float),
-                "fgr_segnorm_bwd: workspace too small (fgr_segnorm_workspace + 8 n_seg c bytes)");
-    const int nch = seg_chunks(max_seg_len);
-    double* part = (double*)ws;
-    float* sums = (float*)((char*)ws + part_bytes);
-    SegApply p{{x, row_div, seg_off, n_seg, c, nch}, n, mean, rstd, gamma, beta, act,
-               has_residual ? y : nullptr, post_act};
-    hipStream_t st = as_stream(stream);
-    const bool vec = seg_vec_ok(n, c, {x, dy, has_residual ? y : nullptr, dx, has_residual ? dres : nullptr,
-                                       mean, rstd, gamma, beta, sums});
-    static const bool fuse = [] { const char* e = getenv("FGR_SEG_FUSED"); return !(e && e[0] == '0'); }();
-    if (fuse && vec && n > 0 && nch <= kSegFuseChunksMax) {
-        const dim3 grid(nch, n_seg, (unsigned)ceil_div(c, 64));
-        hipLaunchKernelGGL(segnorm_bwd_stats4_kernel, grid, dim3(256), 0, st, p, dy, y, part);
-        FGR_CHECK_LAUNCH("segnorm_bwd_stats4_kernel");
-        hipLaunchKernelGGL(segnorm_bwd_merge_apply4_kernel, grid, dim3(256), 0, st, p, dy, y,
-                           (const double*)part, dgamma, dbeta, dx, has_residual ? dres : nullptr);
-        FGR_CHECK_LAUNCH("segnorm_bwd_merge_apply4_kernel");
-        return FGR_OK;
-    }
-    if (vec)
-        hipLaunchKernelGGL(segnorm_bwd_stats4_kernel, dim3(nch, n_seg, (unsigned)ceil_div(c, 64)), dim3(256),
-                           0, st, p, dy, y, part);
-    else
-        hipLaunchKernelGGL(segnorm_bwd_stats_kernel, dim3(nch, n_seg, (unsigned)ceil_div(c, 64)), dim3(256),
-                           0, st, p, dy, y, part);
-    FGR_CHECK_LAUNCH("segnorm_bwd_stats_kernel");
-    hipLaunchKernelGGL(segnorm_bwd_merge_kernel, dim3((unsigned)ceil_div((int64_t)n_seg * c, 256)),
-                       dim3(256), 0, st, p.a, (const double*)part, sums, dgamma, dbeta);
-    FGR_CHECK_LAUNCH("segnorm_bwd_merge_kernel");
-    if (n == 0) return FGR_OK;
-    if (vec)
-        hipLaunchKernelGGL(segnorm_bwd_apply4_kernel, dim3((unsigned)ceil_div(n * c / 4, 256)), dim3(256), 0,
-                           st, p, dy, y, (const float*)sums, dx, has_residual ? dres : nullptr);
-    else
-        hipLaunchKernelGGL(segnorm_bwd_apply_kernel, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, st,
-                           p, dy, y, (const float*)sums, dx, has_residual ? dres : nullptr);
-    FGR_CHECK_LAUNCH("segnorm_bwd_apply_kernel");
     return FGR_OK;
 }
 

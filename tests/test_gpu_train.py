@@ -150,47 +150,84 @@ def _segnorm_ref(x, lens, row_div, gamma, beta, act, residual, post, eps=1e-5):
 
 @pytest.mark.parametrize('case', ['instnorm', 'instnorm_rowdiv_leaky', 'instnorm_residual',
                                   'batchnorm_relu', 'batchnorm_residual_relu', 'long_segments',
-                                  'batchnorm_large'])
+                                  'batchnorm_large', 'many_segments', 'many_segments_unfused',
+                                  'misaligned'])
 @pytest.mark.parametrize('c', [72, 70])
 def test_segnorm_backward(gpu, case, c):
     """segnorm_t: InstanceNorm per cloud (with the KPConv row divisor, LeakyReLU, the
     bottleneck's residual + LeakyReLU) and training BatchNorm (one segment, affine, ReLU,
     residual + ReLU) vs the same formulas in fp64; c = 72 runs the float4 kernels, 70 the
     scalar ones. Chunks of 256 rows per segment: <= 16 (merge fused in order), 47
-    (batchnorm_large: the fused four-way merge), 79 (long_segments: separate merges)."""
+    (batchnorm_large: the fused four-way merge), 79 (long_segments: separate merges).
+    many_segments: 70 segments of 0 .. 40 rows (two empty: the merges' zero statistics; two of
+    one row), more than the 64 that the elementwise kernels keep in LDS; its one chunk per
+    segment takes the fused kernels at c = 72, so many_segments_unfused makes the first segment
+    16500 rows (65 chunks: the separate merges and the float4 elementwise kernels with the
+    segment table in global memory). Its bounds are those of long_segments, whose 20000-row
+    segment is longer and runs the same kernels. misaligned: x starts 4 bytes into its buffer,
+    so c = 72 has to take the scalar kernels too; y and dres then have the bits of the aligned
+    run. dx does not: the scalar and the float4 backward have rounded dz - mean(dz) - xhat
+    mean(dz xhat) differently from the start (8759 of 109008 elements differ, by 1.2e-7 at
+    most), so dx is held to its fp64 bound alone."""
     from fgreg import ops
     from fgreg.autograd import segnorm_t
     g = torch.Generator().manual_seed(len(case))
     lens = [700, 300, 1, 513] if case != 'long_segments' else [20000, 9000]
     if case.startswith('batchnorm'):
         lens = [sum(lens)] if case != 'batchnorm_large' else [12000]
+    if case.startswith('many_segments'):
+        lens = [(7 * i) % 41 for i in range(70)]
+        if case == 'many_segments_unfused':
+            lens[0] = 16500
     n = sum(lens)
-    x, x64 = _leaf(torch.randn(n, c, generator=g) * 3 + 5, gpu)
-    rd = (1 + torch.randint(0, 9, (n,), generator=g)).float() if 'rowdiv' in case else None
+    x0 = torch.randn(n, c, generator=g) * 3 + 5
+    x, x64 = _leaf(x0, gpu)
+    rd = (1 + torch.randint(0, 9, (n,), generator=g)).float() \
+        if 'rowdiv' in case or case.startswith('many_segments') else None
     affine = case.startswith('batchnorm')
     gm, gm64 = _leaf(1 + 0.2 * torch.randn(c, generator=g), gpu) if affine else (None, None)
     bt, bt64 = _leaf(0.1 * torch.randn(c, generator=g), gpu) if affine else (None, None)
-    res = 'residual' in case
+    res = 'residual' in case or case.startswith('many_segments') or case == 'misaligned'
     r, r64 = _leaf(torch.randn(n, c, generator=g), gpu) if res else (None, None)
     act = {'instnorm': 'none', 'instnorm_rowdiv_leaky': 'leaky', 'instnorm_residual': 'none',
            'batchnorm_relu': 'relu', 'batchnorm_residual_relu': 'none', 'long_segments': 'leaky',
-           'batchnorm_large': 'relu'}[case]
+           'batchnorm_large': 'relu', 'many_segments': 'leaky', 'many_segments_unfused': 'leaky',
+           'misaligned': 'none'}[case]
     post = 'relu' if case == 'batchnorm_residual_relu' else 'leaky'
     A = {'none': ops.ACT_NONE, 'relu': ops.ACT_RELU, 'leaky': ops.ACT_LEAKY}
     off = ops.offsets(lens, gpu)
-    y = segnorm_t(x, off, lens, row_div=rd.to(gpu) if rd is not None else None, act=A[act],
-                  residual=r, post_act=A[post], gamma=gm, beta=bt)
+    R = torch.randn(n, c, generator=g)
+
+    def run(xin):
+        out = segnorm_t(xin, off, lens, row_div=rd.to(gpu) if rd is not None else None, act=A[act],
+                        residual=r, post_act=A[post], gamma=gm, beta=bt)
+        (out * R.to(gpu)).sum().backward()
+        return out
+
+    if case == 'misaligned':
+        ya = run(x).detach()
+        dxa, dra = x.grad, r.grad
+        r.grad = None
+        buf = torch.empty(n * c + 1, device=gpu)
+        x = buf[1:].view(n, c)
+        x.copy_(x0)
+        x.requires_grad_(True)
+        assert x.data_ptr() % 16 == 4 and x.is_contiguous()
+    y = run(x)
     y64 = _segnorm_ref(x64, lens, rd.double() if rd is not None else None, gm64, bt64, act, r64,
                        post)
-    R = torch.randn(n, c, generator=g)
-    (y * R.to(gpu)).sum().backward()
     (y64 * R.double()).sum().backward()
+    print(case, c, 'y', rel_err(y, y64), 'dx', rel_err(x.grad, x64.grad),
+          'dres', rel_err(r.grad, r64.grad) if res else None)
     assert rel_err(y, y64) < 1e-5
     assert rel_err(x.grad, x64.grad) < 1e-4, rel_err(x.grad, x64.grad)
     if affine:
         assert rel_err(gm.grad, gm64.grad) < 1e-5 and rel_err(bt.grad, bt64.grad) < 1e-5
     if res:
         assert rel_err(r.grad, r64.grad) < 1e-5
+    if case == 'misaligned':
+        print('dx elements differing from the aligned run:', int((x.grad != dxa).sum()))
+        assert torch.equal(y, ya) and torch.equal(r.grad, dra)
 
 
 def test_segnorm_fused_bit_identical(gpu, tmp_path):

@@ -827,7 +827,10 @@ int fgr_corr_head_f16x3(const float* f, int64_t ldf, int32_t m, int32_t d, const
  *  fgr_attention_bwd    softmax attention backward over packed segments (the layout of
  *                       fgr_attention*): dq, dk, dv (each may alias column slices of one
  *                       tensor), head dim 4 / 8 / 16 / 32 / 64, fp32; key segments may be attended by any
- *                       number of query segments.
+ *                       number of query segments; the rows of a key segment that no query
+ *                       segment attends get dk = dv = 0. A non-empty query segment whose key
+ *                       segment is empty (a softmax over nothing) is undefined, here and in
+ *                       every attention entry point.
  *  fgr_corr_attention_bwd  backward of fgr_corr_attention (CorrespondenceDecoder.simple_attention,
  *                       finegrained_regtr.py:328-363): from dout (n_rows, 3) = d corr, writes
  *                       dq = scale dS K and dk = scale dS^T Q (dS = P (dout . xyz_j - dout .
@@ -901,7 +904,9 @@ int fgr_attention_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, 
  * row, key row) -- kept with probability 1 - p and scaled by 1 / (1 - p), the softmax sum
  * over every weight (transformers.py:95-96; common.h attn_drop_hash). The backward with the
  * same seed / p reproduces the forward's mask; head dim 16 / 32 / 64 (the forward: 32 / 64),
- * 16-B aligned rows. Masks are not torch's Philox draws (same distribution). */
+ * 16-B aligned rows; the backward refuses p > 0 on any other shape (FGR_E_ARG, nothing
+ * written). Masks are not torch's Philox draws (same distribution). A (row, head) whose every
+ * weight is dropped gives o = 0 and contributes exactly 0 to dq, dk and dv. */
 int fgr_attention_f16x3_drop(const float* q, int64_t ld_q, const float* k, int64_t ld_k,
                              const float* v, int64_t ld_v, float* o, int64_t ld_o,
                              const int64_t* q_off, const int64_t* kv_off, const int32_t* kv_seg,
@@ -912,7 +917,8 @@ int fgr_attention_f16x3_drop(const float* q, int64_t ld_q, const float* k, int64
 /* Training pair (dropout p >= 0 as the _drop pair): the forward also writes, per (row, head),
  * the log2-sum-exp of the scaled scores to lse (n_rows * n_head floats); the backward reads it
  * back and skips its own max / sum pass over the keys (head dim 16 / 32 / 64, 16-B aligned
- * rows; other shapes recompute it). */
+ * rows; other shapes recompute it and ignore lse). With p > 0 the lse is still that of the
+ * undropped softmax. */
 int fgr_attention_f16x3_train(const float* q, int64_t ld_q, const float* k, int64_t ld_k,
                               const float* v, int64_t ld_v, float* o, int64_t ld_o,
                               const int64_t* q_off, const int64_t* kv_off, const int32_t* kv_seg,

@@ -25,6 +25,8 @@ sum|terms| per family
   attention   out: softmax |v|. Gradients: dS = P o (dP - D) with dP = dO V^T, D = rowsum(P o
               dP); G = P o (|dO| |V|^T + rowsum(P o |dO| |V|^T)) bounds |dS| term by term, so
               dq: scale G |K|, dk: scale G^T |Q|, dv: P^T |dO|. (corr_attention: v = xyz.)
+              The reference and these denominators live in tests/_attn_ref.py (mha), which
+              also carries the dropout mask of the training pair.
   layernorm   (|x| + |mean|) rstd |gamma| + |beta| + |add|.
   res2net     E_0 = |W_0| |h_0| + |b_0|, E_i = |W_i| (E_{i-1} + |h_i|) + |b_i| (ReLU is
               1-Lipschitz, so the error of step i - 1 reaches step i through |W_i|).
@@ -66,6 +68,20 @@ Entry point -> branch -> arguments that select it -> test
     mfma <32>, <64>     dh 32 / 64, aligned, no lse test_attention_bwd_aligned_mfma[32], [64]
     scalar <16/32/64>   ld % 4 != 0, rows misaligned test_attention_bwd_misaligned[16], [32], [64]
     f16x3 (lse)         dh 32 / 64 from attention_t test_gpu_train::test_attention_backward[*-256-8], [*-512-8]
+  fgr_attention_f16x3_train, fgr_attention_f16x3_drop (test_gpu_attention_train.py, routes F1 - F3)
+    v2<32/64, false> + lse   p = 0                  test_forward_train[*-32], [*-64]
+    v2<32/64, true> + lse    p > 0                  test_forward_train_dropout[*-32], [*-64]
+    v2<32/64, true>          _drop                  test_forward_drop[*-32], [*-64]
+  fgr_attention_bwd_train, fgr_attention_bwd_drop (test_gpu_attention_train.py, routes R1 - R6)
+    f16x3 <32/64, false>     ws of _train_workspace, p = 0   test_backward_f16x3[*], _head_stride[p0-*]
+    f16x3 <32/64, true>      the same, p > 0        test_backward_f16x3_dropout[*], _head_stride[drop-*]
+    mfma <16/32/64> lse_in   ws of fgr_attention_bwd_workspace bytes, p = 0
+                                                    test_backward_mfma_lse[*-16], [*-32], [*-64]
+    mfma <16/32/64, true> lse_in  the same, p > 0   test_backward_mfma_lse_dropout[*-16], [*-32], [*-64]
+    mfma <16/32/64, true>    _drop (own pass 1)     test_backward_drop[*-16], [*-32], [*-64]
+    scalar <8>, <32>         dh 8; ld % 4 != 0, rows misaligned (lse recomputed)
+                                                    test_backward_scalar[dh8], [dh32-misaligned]
+    refused                  p > 0 at dh 8 / misaligned  test_backward_dropout_refused[*]
   fgr_corr_attention, fgr_corr_attention_bwd
     <64>, <256>                                     test_gpu_train::test_corr_attention_backward[64], [256]
     <32>, <128>, <512>                              test_corr_attention_widths[32], [128], [512]
@@ -111,9 +127,6 @@ Entry point -> branch -> arguments that select it -> test
                                                     test_gpu_geometry (both modes, both paths)
 
 Branches without a meaningful reference (named, not tested)
-  attn_bwd_*_mfma_kernel<16, true>   dropout backward at head dim 16: fgr_attention_f16x3_drop
-        takes head dim 32 / 64 only, so no forward draws the mask that this backward replays
-        and there is no output to differentiate.
   instnorm_chunk_kernel<0>           unreachable from fgr_instnorm (above).
 """
 import functools
@@ -125,6 +138,7 @@ import torch
 import torch.nn.functional as F
 
 from _arena import SENTINEL, Arena
+from _attn_ref import mha as _mha
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -325,43 +339,6 @@ def test_max_pool_branches(gpu, c, width):
 # ---------------------------------------------------------------------------------------------
 # attention: forward, backward, the correspondence head's
 # ---------------------------------------------------------------------------------------------
-def _mha(q, k, v, qlens, klens, kv_seg, nhead, scale, R=None, dens=None):
-    """Packed-segment multi-head softmax attention in the dtype of q on the CPU. ``dens`` (a
-    dict): filled with sum|terms| of the output ('o') and, given the cotangent R, of the three
-    gradients ('dq', 'dk', 'dv'); see the module docstring."""
-    d = q.shape[1]
-    dh = d // nhead
-    qo, ko = np.cumsum([0] + list(qlens)), np.cumsum([0] + list(klens))
-    out = torch.zeros(q.shape[0], v.shape[1], dtype=q.dtype)
-    dv_w = v.shape[1] // nhead
-    if dens is not None:
-        dens['o'] = torch.zeros_like(out)
-        for name, t in (('dq', q), ('dk', k), ('dv', v)):
-            dens[name] = torch.zeros(t.shape, dtype=q.dtype)
-    outs = []
-    for i in range(len(qlens)):
-        j = kv_seg[i]
-        heads = []
-        for h in range(nhead):
-            qs = q[qo[i]:qo[i + 1], h * dh:(h + 1) * dh]
-            ks = k[ko[j]:ko[j + 1], h * dh:(h + 1) * dh]
-            vs = v[ko[j]:ko[j + 1], h * dv_w:(h + 1) * dv_w]
-            p = torch.softmax((qs * scale) @ ks.t(), -1)
-            heads.append(p @ vs)
-            if dens is not None:
-                with torch.no_grad():
-                    dens['o'][qo[i]:qo[i + 1], h * dv_w:(h + 1) * dv_w] = p @ vs.abs()
-                    if R is not None:
-                        do = R[qo[i]:qo[i + 1], h * dv_w:(h + 1) * dv_w].abs()
-                        a = do @ vs.abs().t()
-                        g = p * (a + (p * a).sum(-1, keepdim=True))
-                        dens['dq'][qo[i]:qo[i + 1], h * dh:(h + 1) * dh] += scale * (g @ ks.abs())
-                        dens['dk'][ko[j]:ko[j + 1], h * dh:(h + 1) * dh] += scale * (g.t() @ qs.abs())
-                        dens['dv'][ko[j]:ko[j + 1], h * dv_w:(h + 1) * dv_w] += p.t() @ do
-        outs.append(torch.cat(heads, 1))
-    return torch.cat(outs, 0)
-
-
 QLENS, KLENS, KV_SEG = [130, 1, 64, 65], [65, 200, 1, 64], [1, 0, 3, 2]
 
 

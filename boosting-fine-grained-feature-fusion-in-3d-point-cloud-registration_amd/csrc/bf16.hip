@@ -70,12 +70,7 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
     __shared__ u32x4 a_lds[2 * ASZ];
 
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    int t = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    const int t = xcd_tile(blockIdx.x, nbm * nbn);
     const int bm = t / nbn, bn = t % nbn;
     const int m0 = bm * BM, n0 = bn * BN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
@@ -100,26 +95,7 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
     float4 ar[UA][2];
     auto load_a = [&](int s) {
 #pragma unroll
-        for (int j = 0; j < UA; ++j) {
-            const int k = s * 32 + akk[j];
-            if constexpr (KVEC) {
-                const float* src = arow[j] + min(k, p.K - 8);
-                const float4 x0 = *reinterpret_cast<const float4*>(src);
-                const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
-                const bool ok = k < p.K;
-                ar[j][0] = ok ? x0 : make_float4(0.f, 0.f, 0.f, 0.f);
-                ar[j][1] = ok ? x1 : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float tt[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float xv = arow[j][min(k + e, p.K - 1)];
-                    tt[e] = k + e < p.K ? xv : 0.f;
-                }
-                ar[j][0] = make_float4(tt[0], tt[1], tt[2], tt[3]);
-                ar[j][1] = make_float4(tt[4], tt[5], tt[6], tt[7]);
-            }
-        }
+        for (int j = 0; j < UA; ++j) load_a8<KVEC>(arow[j], s * 32 + akk[j], p.K, ar[j]);
     };
     auto store_a = [&](int b) {
         u32x4* a_img = a_lds + b * ASZ;

@@ -155,11 +155,7 @@ __global__ void __launch_bounds__(256, 1) ffn_f16x3_kernel(FfnArgs p) {
     __shared__ float4 lng[kFfnD / 4], lnb[kFfnD / 4];           // LayerNorm3 gamma / beta
 
     const int nbm = (p.M + 63) / 64;
-    int t = blockIdx.x;
-    {   // XCD-aware order: each XCD a contiguous range of row blocks
-        const int q = nbm / 8, r = nbm % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    const int t = xcd_tile(blockIdx.x, nbm);    // each XCD a contiguous range of row blocks
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
     const int mw = t * 64 + wv * 16;                   // this wave's first row
@@ -454,11 +450,7 @@ __global__ void __launch_bounds__(256, 1) ffn_nsplit_kernel(FfnArgs p) {
 
     constexpr int BR = 16 * RT;                           // rows per block
     const int nbm = (p.M + BR - 1) / BR;
-    int t = blockIdx.x;
-    {   // XCD-aware order: each XCD a contiguous range of row blocks
-        const int q = nbm / 8, r = nbm % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    const int t = xcd_tile(blockIdx.x, nbm);    // each XCD a contiguous range of row blocks
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
     const int r0 = t * BR;                                // the block's first row

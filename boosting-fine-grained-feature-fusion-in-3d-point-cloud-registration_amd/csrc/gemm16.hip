@@ -22,11 +22,18 @@
 // ONE activation row (its column c): the per-row scale is lane-local and the epilogue
 // stores 16-B float4s of C.
 //
-// Tiling: 256-thread blocks, 2 x 2 waves over (n, m), block tile BN x BM x 32. W images are
-// flat-copied into LDS; A (fp32) is split in registers while staging into a
-// [term][g][row ^ 2g] LDS image (conflict-free 16-B stores and ds_read_b128 fragment
-// loads); the per-row scale exponents go through a small LDS array. Block ids are
-// remapped so the blocks sharing an A row panel run on one XCD (its L2 keeps the panel).
+// Tiling: 256-thread blocks over a BN x BM block tile, k-looped in 32-wide steps. A (fp32)
+// is split in registers while staging into a [term][g][row ^ 2g] LDS image (conflict-free
+// 16-B stores and ds_read_b128 fragment loads); the per-row scale exponents go through a
+// small LDS array. Block ids are remapped so the blocks sharing an A row panel run on one
+// XCD (its L2 keeps the panel). Three kernels, built from one set of parts (chunk_max8,
+// split_a8, rescale_rows, mma_h3, store_out4, store_tile_h3 below; xcd_tile, load_a8 in
+// mfma.h):
+//   v1  64 x 128, 2 x 2 waves over (n, m), W images flat-copied into LDS too, one k32-step
+//       per stage, one buffer; optionally a staged row-major epilogue
+//   v2  the same wave layout for any tile; 1 or 2 k32-steps per stage, single- or
+//       double-buffered
+//   v4  4 waves over n, W fragments from the image straight into registers
 // 16x16x32 f16 lane maps (lane l, g = l >> 4, c = l & 15): A[i = c][k = 8g + e],
 // B[k = 8g + e][j = c], C[i = 4g + r][j = c].
 #include <cstring>
@@ -35,8 +42,6 @@
 
 namespace fgr {
 namespace {
-
-constexpr int SH_UNSET = 0x3fff;     // "no non-zero chunk seen yet" (partial sums are 0)
 
 struct GemmH3Args {
     const float* A; int64_t lda;
@@ -47,6 +52,66 @@ struct GemmH3Args {
     const float* R; int64_t ldr;
     int M, N, K, act, vec_out;
 };
+
+// ---- the parts v1, v2 and v4 are built from (the XCD order and the A unit load, which the bf16
+// GEMM shares, are in mfma.h) -----------------------------------------------------------
+
+// Staging of one A unit (8 k of one row; RU units = lanes per row and stage, 4 or 8), the
+// precision-critical step, in three moves: chunk_max8, the stage's max |x| over the row's
+// lanes by DPP; the lowering rule, one line in each kernel's store ("if (cm > 0.f && ...) sh[j]
+// = chunk_shift(cm)": the row's scale exponent is lowered when this stage would pass 2^15,
+// and set from the first non-zero one; inside a function it compiled to other code in the
+// kernels that stage several units per thread, so it is a line, not a call); split_a8, the
+// two-term fp16 split of x * 2^sh: x = th + tm to 2^-22.
+template <int RU>
+__device__ __forceinline__ float chunk_max8(const float4 (&ar)[2]) {
+    static_assert(RU == 4 || RU == 8, "lanes per row");
+    const float x[8] = {ar[0].x, ar[0].y, ar[0].z, ar[0].w, ar[1].x, ar[1].y, ar[1].z, ar[1].w};
+    float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
+    cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
+    cm = fmaxf(cm, dpp<0xB1>(cm));              // the row's lanes: quad xor 1, xor 2,
+    cm = fmaxf(cm, dpp<0x4E>(cm));
+    if constexpr (RU == 8) cm = fmaxf(cm, dpp<0x141>(cm));   // + half-row mirror
+    return cm;
+}
+__device__ __forceinline__ void split_a8(const float4 (&ar)[2], int sh, f16x8& th, f16x8& tm) {
+    const float x[8] = {ar[0].x, ar[0].y, ar[0].z, ar[0].w, ar[1].x, ar[1].y, ar[1].z, ar[1].w};
+    const float s = __builtin_ldexpf(1.f, sh == SH_UNSET ? 0 : sh);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float xs = x[e] * s;
+        const _Float16 h = (_Float16)xs;
+        th[e] = h;
+        tm[e] = (_Float16)(xs - (float)h);
+    }
+}
+
+// Rows whose scale was lowered by this stage: rescale their partial sums (exact, rare) and
+// take the new exponents over. shp: the staged exponent of the lane's first row (row 16 i
+// of the lane is 16 i further on).
+template <int TN, int TM>
+__device__ __forceinline__ void rescale_rows(f32x4 (&acc)[TN][TM], int (&shr)[TM], const int* shp) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int shv = shp[16 * i];
+        if (__builtin_amdgcn_ballot_w64(shv != shr[i])) {
+            const float f = (shr[i] == SH_UNSET || shv == shr[i])
+                                ? 1.f : __builtin_ldexpf(1.f, shv - shr[i]);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[j][i] *= f;
+            shr[i] = shv;
+        }
+    }
+}
+
+// the three significant products of a 16x16x32 step (W terms wh + wl, A terms ah + am), the
+// small ones first
+__device__ __forceinline__ void mma_h3(const f16x8& wh, const f16x8& wl, const f16x8& ah,
+                                       const f16x8& am, f32x4& acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, am, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah, acc, 0, 0, 0);
+}
 
 // Stores one lane's 4 consecutive outputs n..n+3 of a row (16-B accesses when vec and the
 // 4 columns are in range).
@@ -69,11 +134,26 @@ __device__ __forceinline__ void store_out4(const float (&y)[4], const float* bia
     }
 }
 
-// EPI: staged epilogue -- each wave's scaled (BM/2) x (BN/2) tile parked in LDS (sharing the
-// A / W image space) and written row-major, 16 B per lane over whole row slices.
+// Row epilogue from the MFMA layout: the lane's 4 accumulators a = C[m][n .. n + 3], times
+// its row's 2^-shr (rs; 0 for an all-zero row) and the columns' W scales (wsc is padded to 16).
+__device__ __forceinline__ void store_tile_h3(const GemmH3Args& p, const f32x4& a, float rs,
+                                              const float* rrow, float* crow, int n) {
+    const float4 ws = *reinterpret_cast<const float4*>(p.wsc + n);
+    const float y[4] = {a[0] * rs * ws.x, a[1] * rs * ws.y, a[2] * rs * ws.z, a[3] * rs * ws.w};
+    store_out4(y, p.bias, rrow, crow, n, p.N, p.act, p.vec_out);
+}
+
+// ------------------------------------------------------------------------------------
+// v1: the 64 x 128 tile of 'b' and 'y', 2 x 2 waves over (n, m), A and W both staged through
+// one LDS buffer, one k32-step per stage. It is v2<64, 128, 1, false> in structure; as that
+// instantiation it measured 1.2-2.9 % slower on long-K shapes, so it keeps a body
+// of its own, built from the same parts but for the epilogue products.
+// EPI ('y'): staged epilogue -- each wave's scaled (BM/2) x (BN/2) tile parked in LDS (sharing
+// the A / W image space) and written row-major, 16 B per lane over whole row slices.
+// ------------------------------------------------------------------------------------
 template <bool KVEC, bool EPI>
 __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
-    constexpr int BM = 64, BN = 128;                    // v1's one tile ('b', 'y')
+    constexpr int BM = 64, BN = 128;
     constexpr int TM = BM / 32, TN = BN / 32;          // 16x16 subtiles per wave (m, n)
     constexpr int UA = BM * 4 / 256;                    // A units (8 k of one row) per thread
     constexpr int UW = 8 * BN / 256;                    // W image units per thread
@@ -85,15 +165,9 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
     u32x4* w_lds = img_lds + 2 * 4 * BM;
     __shared__ int sh_lds[BM];
 
-    // XCD-aware order: hardware dispatches block b to XCD b % 8; remap (bijectively) so that
-    // each XCD gets a contiguous range of tiles, tiles ordered n-fastest within a row panel.
+    // tiles ordered n-fastest within a row panel: the blocks sharing an A panel on one XCD
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    int t = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    const int t = xcd_tile(blockIdx.x, nbm * nbn);
     const int bm = t / nbn, bn = t % nbn;
     const int m0 = bm * BM, n0 = bn * BN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
@@ -121,26 +195,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
     u32x4 wr[UW];
     auto load = [&](int s) {
 #pragma unroll
-        for (int j = 0; j < UA; ++j) {
-            const int k = s * 32 + akk[j];
-            if constexpr (KVEC) {
-                const float* src = arow[j] + min(k, p.K - 8);
-                const float4 x0 = *reinterpret_cast<const float4*>(src);
-                const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
-                const bool ok = k < p.K;
-                ar[j][0] = ok ? x0 : make_float4(0.f, 0.f, 0.f, 0.f);
-                ar[j][1] = ok ? x1 : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float tt[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float xv = arow[j][min(k + e, p.K - 1)];
-                    tt[e] = k + e < p.K ? xv : 0.f;
-                }
-                ar[j][0] = make_float4(tt[0], tt[1], tt[2], tt[3]);
-                ar[j][1] = make_float4(tt[4], tt[5], tt[6], tt[7]);
-            }
-        }
+        for (int j = 0; j < UA; ++j) load_a8<KVEC>(arow[j], s * 32 + akk[j], p.K, ar[j]);
 #pragma unroll
         for (int j = 0; j < UW; ++j) wr[j] = wsrc[j][(int64_t)s * 128];
     };
@@ -149,22 +204,10 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
         for (int j = 0; j < UA; ++j) {
             const int u = tid + 256 * j;
             const int row = u >> 2, gg = u & 3;
-            const float x[8] = {ar[j][0].x, ar[j][0].y, ar[j][0].z, ar[j][0].w,
-                                ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
-            float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
-            cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dpp<0xB1>(cm));              // the row's 4 lanes: quad xor 1, xor 2
-            cm = fmaxf(cm, dpp<0x4E>(cm));
+            const float cm = chunk_max8<4>(ar[j]);
             if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
-            const float s = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
             f16x8 th, tm;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xs = x[e] * s;
-                const _Float16 h = (_Float16)xs;
-                th[e] = h;
-                tm[e] = (_Float16)(xs - (float)h);
-            }
+            split_a8(ar[j], sh[j], th, tm);
             const int r = row ^ (2 * gg);
             a_lds[(0 * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, th);
             a_lds[(1 * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, tm);
@@ -190,18 +233,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
         store();
         __syncthreads();
         if (s + 1 < nk) load(s + 1);
-        // rows whose scale was lowered this step: rescale their partial sums (exact, rare)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int shv = sh_lds[wm + 16 * i + c];
-            if (__builtin_amdgcn_ballot_w64(shv != shr[i])) {
-                const float f = (shr[i] == SH_UNSET || shv == shr[i])
-                                    ? 1.f : __builtin_ldexpf(1.f, shv - shr[i]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[j][i] *= f;
-                shr[i] = shv;
-            }
-        }
+        rescale_rows(acc, shr, &sh_lds[wm + c]);
         f16x8 af[TM][2];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -215,11 +247,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
             const f16x8 wh = __builtin_bit_cast(f16x8, w_lds[pp * 128 + (0 * 4 + g) * 16 + c]);
             const f16x8 wl = __builtin_bit_cast(f16x8, w_lds[pp * 128 + (1 * 4 + g) * 16 + c]);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, af[i][0], acc[j][i], 0, 0, 0);
-                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, af[i][1], acc[j][i], 0, 0, 0);
-                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, af[i][0], acc[j][i], 0, 0, 0);
-            }
+            for (int i = 0; i < TM; ++i) mma_h3(wh, wl, af[i][0], af[i][1], acc[j][i]);
         }
     }
 
@@ -256,7 +284,9 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
             return;
         }
     }
-    // epilogue: lane holds C[m = m0 + wm + 16i + c][n = n0 + wn + 16j + 4g + r], r = 0..3
+    // the lane holds C[m = m0 + wm + 16i + c][n = n0 + wn + 16j + 4g + r], r = 0..3
+    // (store_tile_h3's product spelled out, as in the staged block above: with it this
+    // kernel's code is instruction for instruction what it was before the parts were shared)
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + wm + 16 * i + c;
@@ -277,14 +307,15 @@ __global__ void __launch_bounds__(256) gemm_f16x3_kernel(GemmH3Args p) {
 }
 
 // ------------------------------------------------------------------------------------
-// v2: KS k32-steps per staged tile (one row scale per KS*32 chunk, one barrier pair per
-// stage instead of per k32-step) and optionally double-buffered LDS (DBUF: one barrier per
-// stage; the next stage's split + LDS store overlaps other waves' MFMAs).
+// v2: 2 x 2 waves over (n, m); A and W both staged through LDS, KS k32-steps per staged tile
+// (one row scale per KS*32 chunk, one barrier pair per stage) and optionally double-buffered
+// (DBUF: one barrier per stage; the next stage's split + LDS store overlaps other waves'
+// MFMAs).
 // LDS images per stage: A [ks][term 2][g 4][BM rows ^ 2g], W [panel][ks][term 2][g 4][16].
 // ------------------------------------------------------------------------------------
 template <int BM, int BN, int KS, bool DBUF, bool KVEC>
 __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
-    constexpr int TM = BM / 32, TN = BN / 32;
+    constexpr int TM = BM / 32, TN = BN / 32;           // 16x16 subtiles per wave (m, n)
     constexpr int RU = 4 * KS;                          // units (8 k) of a row per stage
     constexpr int UA = BM * RU / 256;                   // A units per thread per stage
     constexpr int UW = 8 * BN * KS / 256;               // W units per thread per stage
@@ -294,13 +325,9 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
     __shared__ u32x4 lds[NB * (ASZ + WSZ)];
     __shared__ int sh_lds[NB][BM];
 
+    // tiles ordered n-fastest within a row panel: the blocks sharing an A panel on one XCD
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    int t = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    const int t = xcd_tile(blockIdx.x, nbm * nbn);
     const int bm = t / nbn, bn = t % nbn;
     const int m0 = bm * BM, n0 = bn * BN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
@@ -328,26 +355,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
     u32x4 wr[UW];
     auto load = [&](int s) {
 #pragma unroll
-        for (int j = 0; j < UA; ++j) {
-            const int k = s * 32 * KS + akk[j];
-            if constexpr (KVEC) {
-                const float* src = arow[j] + min(k, p.K - 8);
-                const float4 x0 = *reinterpret_cast<const float4*>(src);
-                const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
-                const bool ok = k < p.K;
-                ar[j][0] = ok ? x0 : make_float4(0.f, 0.f, 0.f, 0.f);
-                ar[j][1] = ok ? x1 : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float tt[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float xv = arow[j][min(k + e, p.K - 1)];
-                    tt[e] = k + e < p.K ? xv : 0.f;
-                }
-                ar[j][0] = make_float4(tt[0], tt[1], tt[2], tt[3]);
-                ar[j][1] = make_float4(tt[4], tt[5], tt[6], tt[7]);
-            }
-        }
+        for (int j = 0; j < UA; ++j) load_a8<KVEC>(arow[j], s * 32 * KS + akk[j], p.K, ar[j]);
 #pragma unroll
         for (int j = 0; j < UW; ++j) wr[j] = wsrc[j][(int64_t)s * 128 * KS];
     };
@@ -358,23 +366,10 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
         for (int j = 0; j < UA; ++j) {
             const int u = tid + 256 * j;
             const int row = u / RU, q = u % RU, ks = q >> 2, gg = q & 3;
-            const float x[8] = {ar[j][0].x, ar[j][0].y, ar[j][0].z, ar[j][0].w,
-                                ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
-            float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
-            cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dpp<0xB1>(cm));              // the row's lanes: quad xor 1, xor 2,
-            cm = fmaxf(cm, dpp<0x4E>(cm));
-            if constexpr (RU == 8) cm = fmaxf(cm, dpp<0x141>(cm));   // + half-row mirror
+            const float cm = chunk_max8<RU>(ar[j]);
             if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
-            const float s = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
             f16x8 th, tm;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xs = x[e] * s;
-                const _Float16 h = (_Float16)xs;
-                th[e] = h;
-                tm[e] = (_Float16)(xs - (float)h);
-            }
+            split_a8(ar[j], sh[j], th, tm);
             const int r = row ^ (2 * gg);
             a_img[((ks * 2 + 0) * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, th);
             a_img[((ks * 2 + 1) * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, tm);
@@ -389,24 +384,14 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
     for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int shr[TM];
+    int shr[TM];                                       // scale exponent of this lane's rows
 #pragma unroll
     for (int i = 0; i < TM; ++i) shr[i] = SH_UNSET;
 
     auto compute = [&](int b) {
         const u32x4* a_img = lds + b * (ASZ + WSZ);
         const u32x4* w_img = a_img + ASZ;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int shv = sh_lds[b][wm + 16 * i + c];
-            if (__builtin_amdgcn_ballot_w64(shv != shr[i])) {
-                const float f = (shr[i] == SH_UNSET || shv == shr[i])
-                                    ? 1.f : __builtin_ldexpf(1.f, shv - shr[i]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[j][i] *= f;
-                shr[i] = shv;
-            }
-        }
+        rescale_rows(acc, shr, &sh_lds[b][wm + c]);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             f16x8 af[TM][2];
@@ -423,11 +408,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
                 const f16x8 wh = __builtin_bit_cast(f16x8, wb[0]);
                 const f16x8 wl = __builtin_bit_cast(f16x8, wb[64]);
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, af[i][0], acc[j][i], 0, 0, 0);
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, af[i][1], acc[j][i], 0, 0, 0);
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, af[i][0], acc[j][i], 0, 0, 0);
-                }
+                for (int i = 0; i < TM; ++i) mma_h3(wh, wl, af[i][0], af[i][1], acc[j][i]);
             }
         }
     };
@@ -455,6 +436,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
         }
     }
 
+    // the lane holds C[m = m0 + wm + 16i + c][n = n0 + wn + 16j + 4g + r], r = 0..3
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + wm + 16 * i + c;
@@ -466,10 +448,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v2(GemmH3Args p) {
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + wn + 16 * j + 4 * g;
             if (n >= p.N) continue;
-            const float4 ws = *reinterpret_cast<const float4*>(p.wsc + n);
-            const float y[4] = {acc[j][i][0] * rs * ws.x, acc[j][i][1] * rs * ws.y,
-                                acc[j][i][2] * rs * ws.z, acc[j][i][3] * rs * ws.w};
-            store_out4(y, p.bias, rrow, crow, n, p.N, p.act, p.vec_out);
+            store_tile_h3(p, acc[j][i], rs, rrow, crow, n);
         }
     }
 }
@@ -496,12 +475,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
     __shared__ int sh_lds[2][BM];
 
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    int t = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    const int t = xcd_tile(blockIdx.x, nbm * nbn);
     const int bm = t / nbn, bn = t % nbn;
     const int m0 = bm * BM, n0 = bn * BN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
@@ -528,26 +502,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
     float4 ar[UA][2];
     auto load_a = [&](int s) {
 #pragma unroll
-        for (int j = 0; j < UA; ++j) {
-            const int k = s * 32 + akk[j];
-            if constexpr (KVEC) {
-                const float* src = arow[j] + min(k, p.K - 8);
-                const float4 x0 = *reinterpret_cast<const float4*>(src);
-                const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
-                const bool ok = k < p.K;
-                ar[j][0] = ok ? x0 : make_float4(0.f, 0.f, 0.f, 0.f);
-                ar[j][1] = ok ? x1 : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float tt[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float xv = arow[j][min(k + e, p.K - 1)];
-                    tt[e] = k + e < p.K ? xv : 0.f;
-                }
-                ar[j][0] = make_float4(tt[0], tt[1], tt[2], tt[3]);
-                ar[j][1] = make_float4(tt[4], tt[5], tt[6], tt[7]);
-            }
-        }
+        for (int j = 0; j < UA; ++j) load_a8<KVEC>(arow[j], s * 32 + akk[j], p.K, ar[j]);
     };
     auto store_a = [&](int b) {
         u32x4* a_img = a_lds + b * ASZ;
@@ -555,22 +510,10 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
         for (int j = 0; j < UA; ++j) {
             const int u = tid + 256 * j;
             const int row = u >> 2, gg = u & 3;
-            const float x[8] = {ar[j][0].x, ar[j][0].y, ar[j][0].z, ar[j][0].w,
-                                ar[j][1].x, ar[j][1].y, ar[j][1].z, ar[j][1].w};
-            float cm = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
-            cm = fmaxf(cm, fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-            cm = fmaxf(cm, dpp<0xB1>(cm));
-            cm = fmaxf(cm, dpp<0x4E>(cm));
+            const float cm = chunk_max8<4>(ar[j]);
             if (cm > 0.f && __builtin_amdgcn_frexp_expf(cm) + sh[j] > 15) sh[j] = chunk_shift(cm);
-            const float sc = __builtin_ldexpf(1.f, sh[j] == SH_UNSET ? 0 : sh[j]);
             f16x8 th, tm;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xs = x[e] * sc;
-                const _Float16 h = (_Float16)xs;
-                th[e] = h;
-                tm[e] = (_Float16)(xs - (float)h);
-            }
+            split_a8(ar[j], sh[j], th, tm);
             const int r = row ^ (2 * gg);
             a_img[(0 * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, th);
             a_img[(1 * 4 + gg) * BM + r] = __builtin_bit_cast(u32x4, tm);
@@ -597,30 +540,16 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
 
     auto compute = [&](int b, const u32x4 (&w)[TN][2]) {
         const u32x4* a_img = a_lds + b * ASZ;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int shv = sh_lds[b][16 * i + c];
-            if (__builtin_amdgcn_ballot_w64(shv != shr[i])) {
-                const float f = (shr[i] == SH_UNSET || shv == shr[i])
-                                    ? 1.f : __builtin_ldexpf(1.f, shv - shr[i]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[j][i] *= f;
-                shr[i] = shv;
-            }
-        }
+        rescale_rows(acc, shr, &sh_lds[b][c]);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int r = (16 * i + c) ^ (2 * g);
             const f16x8 ah = __builtin_bit_cast(f16x8, a_img[(0 * 4 + g) * BM + r]);
             const f16x8 am = __builtin_bit_cast(f16x8, a_img[(1 * 4 + g) * BM + r]);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const f16x8 wh = __builtin_bit_cast(f16x8, w[j][0]);
-                const f16x8 wl = __builtin_bit_cast(f16x8, w[j][1]);
-                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah, acc[j][i], 0, 0, 0);
-                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, am, acc[j][i], 0, 0, 0);
-                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah, acc[j][i], 0, 0, 0);
-            }
+            for (int j = 0; j < TN; ++j)
+                mma_h3(__builtin_bit_cast(f16x8, w[j][0]), __builtin_bit_cast(f16x8, w[j][1]), ah,
+                       am, acc[j][i]);
         }
     };
 
@@ -644,7 +573,6 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
         }
         compute(1, w1);
     }
-
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + 16 * i + c;
@@ -656,10 +584,7 @@ __global__ void __launch_bounds__(256) gemm_f16x3_v4(GemmH3Args p) {
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + wn + 16 * j + 4 * g;
             if (n >= p.N) continue;
-            const float4 ws = *reinterpret_cast<const float4*>(p.wsc + n);
-            const float y[4] = {acc[j][i][0] * rs * ws.x, acc[j][i][1] * rs * ws.y,
-                                acc[j][i][2] * rs * ws.z, acc[j][i][3] * rs * ws.w};
-            store_out4(y, p.bias, rrow, crow, n, p.N, p.act, p.vec_out);
+            store_tile_h3(p, acc[j][i], rs, rrow, crow, n);
         }
     }
 }
@@ -874,15 +799,6 @@ split_weights_h3_batch_kernel(const fgr_split_desc* __restrict__ d, int count) {
     split_panel_h3(e.w, e.n, e.k, e.stride_n, e.stride_k, ksteps, wsc, img, (int)(b - e.panel0));
 }
 
-template <bool EPI>
-void launch_h3(const GemmH3Args& a, hipStream_t st) {
-    const int nbm = (a.M + 63) / 64, nbn = (a.N + 127) / 128;
-    if (a.K % 8 == 0)
-        hipLaunchKernelGGL((gemm_f16x3_kernel<true, EPI>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((gemm_f16x3_kernel<false, EPI>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, st, a);
-}
-
 // k32-steps of the image, padded to an even count (v2 stages read 2 per stage)
 int ksteps_h3(int k) { return (k + 63) / 64 * 2; }
 
@@ -910,6 +826,15 @@ void launch_h3v2(const GemmH3Args& a, hipStream_t st) {
     else
         hipLaunchKernelGGL((gemm_f16x3_v2<BM, BN, KS, DBUF, false>), dim3((unsigned)(nbm * nbn)),
                            dim3(256), 0, st, a);
+}
+
+template <bool EPI>
+void launch_h3(const GemmH3Args& a, hipStream_t st) {
+    const int nbm = (a.M + 63) / 64, nbn = (a.N + 127) / 128;
+    if (a.K % 8 == 0)
+        hipLaunchKernelGGL((gemm_f16x3_kernel<true, EPI>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((gemm_f16x3_kernel<false, EPI>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, st, a);
 }
 
 }  // namespace

@@ -35,8 +35,6 @@ namespace {
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-constexpr int SH_UNSET = 0x3fff;
-
 // 16 zero bytes: the DMA source of A chunks past K (the LDS image gets exact zeros, so no
 // register-side masking is needed)
 __device__ __attribute__((aligned(16))) float g5_zero[4];
@@ -96,11 +94,7 @@ __global__ void __launch_bounds__(256 * KW) gemm_g5(G5Args p) {
 
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
     const int nwg = nbm * nbn, ntot = nwg * p.ksplit;
-    int t = blockIdx.x;
-    {   // XCD-aware bijective remap: consecutive tiles (n fastest) on one XCD
-        const int q = ntot / 8, r = ntot % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    int t = xcd_tile(blockIdx.x, ntot);        // consecutive tiles (n fastest) on one XCD
     const int kz = t / nwg;                    // split-K part (0 without split)
     t %= nwg;
     const int bm = t / nbn, bn = t % nbn;

@@ -146,11 +146,8 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
     const int npanel = (p.N + 15) / 16;
     const int ngrp = (npanel + p.nc - 1) / p.nc;
     const int nwg = nbm * ngrp;
-    int t = blockIdx.x;
-    {   // XCD-aware order: each XCD a contiguous range, the column groups of a row block adjacent
-        const int q = nwg / 8, r = nwg % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    // each XCD a contiguous range, the column groups of a row block adjacent
+    const int t = xcd_tile(blockIdx.x, nwg);
     const int bm = t / ngrp, grp = t % ngrp;
     const int p0 = grp * p.nc;
     const int np = min(p.nc, npanel - p0);             // block-uniform

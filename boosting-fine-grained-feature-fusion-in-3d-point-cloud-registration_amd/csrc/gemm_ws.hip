@@ -100,11 +100,7 @@ gemm_ws_kernel(WsArgs p) {
     __shared__ float4 side[kSideLds ? BR * 64 : 1];
 
     const int nblk = (p.M + BR - 1) / BR * NPART;
-    int t = blockIdx.x;
-    {   // XCD-aware order: each XCD a contiguous range of (row block, part)
-        const int q = nblk / 8, r = nblk % 8, x = t % 8, lo = t / 8;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
-    }
+    int t = xcd_tile(blockIdx.x, nblk);         // each XCD a contiguous range of (row block, part)
     const int part = t % NPART;
     t /= NPART;                                           // the row block
     const int cb4 = part * (N / 4);                       // the part's first column / 4

@@ -1,6 +1,7 @@
 // Device helpers shared by the matrix-core kernels (gfx950 / CDNA4, wave64): vector types,
-// reductions across the four 16-lane rows, the f16x3 scale exponents, s_waitcnt encodings
-// and the GEMM epilogue. One definition each; all force-inlined.
+// reductions across the four 16-lane rows, the f16x3 scale exponents, the XCD block order,
+// the register-staged GEMMs' A unit load, s_waitcnt encodings and the GEMM epilogue of one
+// output. One definition each; all force-inlined.
 #pragma once
 #include "common.h"
 
@@ -52,6 +53,40 @@ __device__ __forceinline__ int row_scale_exp(float mx) {
 // cm * 2^sh in [2^7, 2^8)
 __device__ __forceinline__ int chunk_shift(float cm) {
     return min(8 - __builtin_amdgcn_frexp_expf(cm), 127);
+}
+// a row's in-flight scale exponent before its first non-zero chunk (its partial sums are 0)
+constexpr int SH_UNSET = 0x3fff;
+
+// ---- XCD-aware block order: hardware dispatches block t to XCD t % 8; the bijective remap
+// of 0..n-1 that gives each XCD a contiguous range of tiles (its L2 keeps what neighbouring
+// tiles share)
+__device__ __forceinline__ int xcd_tile(int t, int n) {
+    const int q = n / 8, r = n % 8, x = t % 8, lo = t / 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lo;
+}
+
+// ---- one A unit of the register-staged GEMMs: the 8 floats arow[k .. k+7] of an activation
+// row of length K, zeros past K. KVEC (K % 8 == 0, 16-B aligned rows): two 16-B loads,
+// address clamped into the row; else scalar loads, each clamped.
+template <bool KVEC>
+__device__ __forceinline__ void load_a8(const float* arow, int k, int K, float4 (&ar)[2]) {
+    if constexpr (KVEC) {
+        const float* src = arow + min(k, K - 8);
+        const float4 x0 = *reinterpret_cast<const float4*>(src);
+        const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
+        const bool ok = k < K;
+        ar[0] = ok ? x0 : make_float4(0.f, 0.f, 0.f, 0.f);
+        ar[1] = ok ? x1 : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        float tt[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float xv = arow[min(k + e, K - 1)];
+            tt[e] = k + e < K ? xv : 0.f;
+        }
+        ar[0] = make_float4(tt[0], tt[1], tt[2], tt[3]);
+        ar[1] = make_float4(tt[4], tt[5], tt[6], tt[7]);
+    }
 }
 
 // ---- s_waitcnt immediates, gfx9 encoding: vmcnt = bits 3:0 and 15:14, expcnt = bits 6:4

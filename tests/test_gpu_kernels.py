@@ -392,9 +392,11 @@ def test_gemm_split_vs_fp64(gpu, m, n, k):
             assert rel_err(fl.linear(X, W, Bb[:h], rows=(0, h)), ref[:, :h]) < tol
 
 
-@pytest.mark.parametrize('tile', ['', 'b', 'I', 'K', 'O', 'S', 'z'])
+@pytest.mark.parametrize('tile', ['', 'b', 'I', 'K', 'O', 'S', 'z', 'e', 'k', 'u', 'y'])
 def test_gemm_f16x3_dynamic_range(gpu, tile, monkeypatch):
-    """f16x3 row scaling (tile: '' the default dispatch, else FGR_GEMM16_TILE) under
+    """f16x3 row scaling (tile: '' the default dispatch, else FGR_GEMM16_TILE; of the
+    register-staged kernels b: v2, e: v2 with two k32-steps per stage (the row maximum over 8
+    lanes), k: v2 double-buffered, u: v4, y: the staged epilogue) under
     adversarial magnitudes: rows at 1e-15 .. 1e15 (far outside fp16's range), all-zero rows, rows whose first k chunks are zero, rows that grow by
     2^40 along k (forces the in-flight rescale of partial sums) and a weight matrix with
     rows at 1e-10 / 1e10 (outputs stay inside fp32's range). Every output row must match fp64 to 2e-6 of its own scale."""

@@ -895,6 +895,43 @@ def attention(q, k, v, q_off, kv_off, kv_seg, max_q_len, n_head, out=None,
     return out
 
 
+def attention_weights(q, k, q_off, kv_off, kv_seg, max_q_len, n_head, max_kv_len=None,
+                      out=None) -> torch.Tensor:
+    """The head-averaged attention maps of ``attention``'s segments (fgr_attention_weights):
+    what nn.MultiheadAttention returns beside its output with need_weights = True.
+
+    q, k: (rows, n_head * dh) fp32 views with unit column stride (may be column slices of one
+    fused QKV tensor), dh a multiple of 4 up to 256. Returns w (Nq, max_kv_len) fp32: row r of
+    query segment i holds mean_h softmax_j(q_h[r] . k_h[j] / sqrt(dh)) over the n keys of
+    segment kv_seg[i] and exact zeros in columns n .. max_kv_len. ``max_kv_len`` defaults to
+    ``max_q_len``. ``out``: (Nq, >= max_kv_len) fp32 with unit column stride; only its first
+    max_kv_len columns are written. Exact fp32 in either precision mode: an inspection path
+    (TransformerCrossEncoder.record_attention), not part of the forward."""
+    _dev(q, k, q_off, kv_off, kv_seg, out)
+    for t in (q, k):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+    d = q.shape[1]
+    assert k.shape[1] == d and d % n_head == 0
+    dh = d // n_head
+    n_seg = q_off.numel() - 1
+    assert kv_seg.dtype == torch.int32 and kv_seg.numel() == n_seg
+    max_kv_len = int(max_q_len if max_kv_len is None else max_kv_len)
+    if out is None:
+        out = torch.empty((q.shape[0], max_kv_len), dtype=torch.float32, device=q.device)
+    assert (out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == q.shape[0]
+            and out.shape[1] >= max_kv_len and (out.stride(1) == 1 or out.shape[1] <= 1))
+    if q.shape[0] == 0 or max_kv_len == 0:          # nothing to write (and no pointers to pass)
+        return out[:, :max_kv_len]
+    ld_w = out.stride(0) if out.shape[0] > 1 else max(out.stride(0), out.shape[1])
+    t0 = _begin('attention_weights')
+    _lib.check(_lib.load().fgr_attention_weights(
+        _ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(out), ld_w, _ptr(q_off), _ptr(kv_off),
+        _ptr(kv_seg), n_seg, int(max_q_len), max_kv_len, n_head, dh,
+        float(math.sqrt(1.0 / float(dh))), _stream()), 'fgr_attention_weights')
+    _end('attention_weights', t0)
+    return out[:, :max_kv_len] if out.shape[1] != max_kv_len else out
+
+
 def attention_lse_ok(q, k, v, n_head) -> bool:
     """True if ops.attention can hand the backward its log-sum-exp (``lse``)."""
     dh = q.shape[1] // n_head

@@ -91,6 +91,10 @@ def pipeline(model: RegTR, batches, depth=None, streams=None):
     (default STREAMS)."""
     if model.training and torch.is_grad_enabled():
         raise NotImplementedError('fgreg.pipeline is inference only (eval() / no_grad)')
+    if model.transformer_encoder.record_attention:
+        # the maps are per-layer state on the modules: overlapped cores would race on it
+        raise NotImplementedError('fgreg.pipeline does not record attention maps: clear '
+                                  'transformer_encoder.record_attention, or call the model')
     depth = max(1, int(DEPTH if depth is None else depth))
     n_streams = max(1, int(STREAMS if streams is None else streams))
     it = iter(batches)

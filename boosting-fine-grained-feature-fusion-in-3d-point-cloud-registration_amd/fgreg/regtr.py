@@ -307,8 +307,12 @@ class RegTR(nn.Module):
             from .training import core_train
             res = core_train(self, meta, self._segments(slens_c, xyz_c), B)
         else:
+            # a recording forward (transformer_encoder.record_attention) always runs eagerly:
+            # it is neither captured nor replayed, does not count as a sighting of its shape
+            # signature, and leaves the model's graphs alone
             core = (_graph_for(self, meta, slens_c, B, slot)
-                    if GRAPHS and xyz_c.is_cuda and ops.TIMER is None else None)
+                    if GRAPHS and xyz_c.is_cuda and ops.TIMER is None
+                    and not self.transformer_encoder.record_attention else None)
             res = core.run(meta) if core is not None else self._core(
                 meta, self._segments(slens_c, xyz_c), B)
         both, feats, corr, logits, pose = res

@@ -143,6 +143,11 @@ def check_trainable(model):
     """Raises NotImplementedError for configurations this training forward does not restate
     (checked before any work, so CPU and GPU callers see the same error)."""
     cfg = model.cfg
+    if model.transformer_encoder.record_attention:
+        # the reference's training maps are post-dropout (nn.MultiheadAttention returns the
+        # dropped weights): not what ops.attention_weights computes
+        raise NotImplementedError('record_attention is inference only: the training forward '
+                                  'records no attention maps')
     if not (cfg.sa_val_has_pos_emb and cfg.ca_val_has_pos_emb):
         raise NotImplementedError('training with value-without-positional-embedding attention is '
                                   'not in the reference configs')

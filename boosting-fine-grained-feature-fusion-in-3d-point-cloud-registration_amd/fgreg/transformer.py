@@ -73,6 +73,15 @@ class Segments:
                                  ops.to_device(v_off, torch.int64, device))
 
 
+class _QKTap(nn.Module):
+    """Identity on (q, k), called only on the recording route with the fp32 in_proj outputs
+    that both ops.attention and ops.attention_weights read: a forward hook on a layer's
+    ``in_proj_tap`` sees exactly what a recorded map was computed from. No parameters."""
+
+    def forward(self, q, k):
+        return q, k
+
+
 class TransformerCrossEncoderLayer(nn.Module):
     """transformers.py:84-258: forward_pre (pre_norm: True, the shipped configs) and
     forward_post (pre_norm: False); dropout must be 0 at inference."""
@@ -104,32 +113,49 @@ class TransformerCrossEncoderLayer(nn.Module):
         self.normalize_before = normalize_before
         self.sa_val_has_pos_emb = sa_val_has_pos_emb
         self.ca_val_has_pos_emb = ca_val_has_pos_emb
+        # the attention maps of the last recording forward (transformers.py:116, 177-179,
+        # 240-242): (src, tgt) pairs of padded (B, Nq_max, Nk_max) head-mean weights
+        self.satt_weights, self.xatt_weights = None, None
+        self.in_proj_tap = _QKTap()
 
-    def _attend(self, mha, h_pos, h_nopos, val_has_pos, seg, kv_seg, ln=None, side=None):
+    def _attention(self, q, k, v, seg, kv_seg, record):
+        """ops.attention on fp32 q / k / v; ``record`` (a list) also receives the packed
+        (N, seg.max_len) head-mean attention map of the same q / k."""
+        if record is not None:
+            q, k = self.in_proj_tap(q, k)
+            record.append(ops.attention_weights(q, k, seg.off, seg.off, kv_seg, seg.max_len,
+                                                self.nhead))
+        return ops.attention(q, k, v, seg.off, seg.off, kv_seg, seg.max_len, self.nhead)
+
+    def _attend(self, mha, h_pos, h_nopos, val_has_pos, seg, kv_seg, ln=None, side=None,
+                record=None):
         """``ln`` = (x, norm, pos): h_pos = norm(x) + pos is formed inside the in_proj GEMM
-        (linear_ln; val_has_pos only); ``side`` = (norm2, out2): out2 = norm2(x) as well."""
+        (linear_ln; val_has_pos only); ``side`` = (norm2, out2): out2 = norm2(x) as well.
+        ``record`` (a list): the recording route. The launches that keep q / k / v out of fp32
+        memory (ln_qkv_attention, qkv_attention) are not taken, and the attention map of the
+        q / k that ops.attention reads is appended to the list."""
         W, b = mha.in_proj_weight, mha.in_proj_bias
         if ln is not None:
             x, norm, pos = ln
             d = x.shape[1]
             # the image path forms norm(x) + pos in its prologue: it needs the pos rows
             # (transformer_encoder_has_pos_emb False -> pos None -> linear_ln below)
-            if (lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3' and pos is not None
-                    and ops.ln_qkv_supported(x.shape[0], d, self.nhead)
+            if (record is None and lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3'
+                    and pos is not None and ops.ln_qkv_supported(x.shape[0], d, self.nhead)
                     and (side is None or side[0].eps == norm.eps)):
                 # k / v straight into the attention's images (no fp32 k / v, no image launch)
                 return ops.ln_qkv_attention(x, norm, lin.weight_image(W, mode='f16x3'), b, pos,
                                             seg.off, kv_seg, seg.max_len, self.nhead, side=side)
             qkv = linear_ln(x, norm, W, b, add=pos, side=side)        # (N, 3d): [q | k | v]
             q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-            return ops.attention(q, k, v, seg.off, seg.off, kv_seg, seg.max_len, self.nhead)
+            return self._attention(q, k, v, seg, kv_seg, record)
         d = h_pos.shape[1]
-        if (val_has_pos and lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3'
+        if (record is None and val_has_pos and lin.MODE == 'f16x3' and ops.ATTN_MODE == 'f16x3'
                 and ops.qkv_supported(h_pos.shape[0], d, self.nhead)):
             # head dim 64: the in_proj writes the attention's K / V images itself
             return ops.qkv_attention(h_pos, lin.weight_image(W, mode='f16x3'), b, seg.off, kv_seg,
                                      seg.max_len, self.nhead)
-        if (val_has_pos and lin.MODE == 'bf16' and ops.ATTN_MODE == 'bf16'
+        if (record is None and val_has_pos and lin.MODE == 'bf16' and ops.ATTN_MODE == 'bf16'
                 and ops.qkv_bf16_supported(h_pos.shape[0], d, self.nhead)):
             return ops.qkv_attention(h_pos, lin.weight_image(W, mode='bf16'), b, seg.off, kv_seg,
                                      seg.max_len, self.nhead, mode='bf16')
@@ -140,8 +166,32 @@ class TransformerCrossEncoderLayer(nn.Module):
             qk = linear(h_pos, W, b[:2 * d], rows=(0, 2 * d))         # [q | k]
             q, k = qk[:, :d], qk[:, d:]
             v = linear(h_nopos, W, b[2 * d:], rows=(2 * d, 3 * d))
-        o = ops.attention(q, k, v, seg.off, seg.off, kv_seg, seg.max_len, self.nhead)
-        return o
+        return self._attention(q, k, v, seg, kv_seg, record)
+
+    def _store_maps(self, packed, seg):
+        """The packed self / cross maps of one recording forward -> satt_weights, xatt_weights
+        in the reference's padded layout: per side (B, Nq_max, Nk_max) with a pair's valid block
+        at [b, :n_q, :n_k] and zeros elsewhere. Padded query rows are zero here (the reference
+        holds a padded query's softmax there; nothing can use those rows). Only the 2B clouds
+        are read: the decoder's query-only phantom segments never appear."""
+        B, lens = seg.B, seg.lengths
+        start = [0]
+        for n in lens:
+            start.append(start[-1] + n)
+
+        def padded(w, cross):
+            sides = []
+            for s in (0, 1):
+                clouds = range(s * B, (s + 1) * B)
+                keys = [(c + B) % (2 * B) if cross else c for c in clouds]
+                t = w.new_zeros((B, max(lens[c] for c in clouds), max(lens[c] for c in keys)))
+                for b, (c, kc) in enumerate(zip(clouds, keys)):
+                    t[b, :lens[c], :lens[kc]] = w[start[c]:start[c + 1], :lens[kc]]
+                sides.append(t)
+            return tuple(sides)
+
+        self.satt_weights = padded(packed[0], False)
+        self.xatt_weights = padded(packed[1], True)
 
     def takes_side(self, x, pos):
         """True if forward_packed can also write another LayerNorm of its input x (``side``)
@@ -157,15 +207,18 @@ class TransformerCrossEncoderLayer(nn.Module):
         return (self.normalize_before and self.sa_val_has_pos_emb
                 and not ln_fusable(n, 3 * d, d))
 
-    def forward_packed(self, x, pos, seg: Segments, pending_bias=None, h1=None, side=None):
+    def forward_packed(self, x, pos, seg: Segments, pending_bias=None, h1=None, side=None,
+                       record=False):
         """x (N_tot, d) packed clouds -> (x, pending bias) (forward_pre, transformers.py:183-244).
+        ``record``: also store this layer's attention maps (satt_weights, xatt_weights).
 
         Every residual GEMM adds its Linear's bias and the residual in its epilogue, so each
         LayerNorm only reads x (no in-place bias pass writing x back); ``pending_bias`` (a
         bias still to be added to x by the first LayerNorm) is accepted for callers that
         defer one, and the returned pending bias is None."""
         if not self.normalize_before:
-            return self._forward_post(x, pos, seg, pending_bias), None
+            return self._forward_post(x, pos, seg, pending_bias, record), None
+        rec = [] if record else None
         n, d = x.shape
         # LayerNorm (+ pos) folded into the next GEMM where that GEMM supports it
         # (linear_ln): the norm output is never written
@@ -173,11 +226,11 @@ class TransformerCrossEncoderLayer(nn.Module):
         # self-attention, shared weights for src and tgt (:193-210)
         if fuse_in and self.sa_val_has_pos_emb and pending_bias is None:
             o = self._attend(self.self_attn, None, None, True, seg, seg.self_seg,
-                             ln=(x, self.norm1, pos), side=side)
+                             ln=(x, self.norm1, pos), side=side, record=rec)
             side = None
         elif h1 is not None:              # norm1(x) + pos from the previous layer's output norm
             assert pending_bias is None and self.sa_val_has_pos_emb
-            o = self._attend(self.self_attn, h1, None, True, seg, seg.self_seg)
+            o = self._attend(self.self_attn, h1, None, True, seg, seg.self_seg, record=rec)
         else:
             if side is not None:
                 ops.layernorm(x, side[0].weight, side[0].bias, side[0].eps, out=side[1])
@@ -186,18 +239,21 @@ class TransformerCrossEncoderLayer(nn.Module):
                               pre_bias=pending_bias)
             h0 = None if self.sa_val_has_pos_emb else ops.layernorm(
                 x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-            o = self._attend(self.self_attn, h, h0, self.sa_val_has_pos_emb, seg, seg.self_seg)
+            o = self._attend(self.self_attn, h, h0, self.sa_val_has_pos_emb, seg, seg.self_seg,
+                             record=rec)
         x = linear(o, self.self_attn.out_proj.weight, self.self_attn.out_proj.bias, residual=x)
         # cross-attention, both directions at once (:212-229)
         if fuse_in and self.ca_val_has_pos_emb:
             o = self._attend(self.multihead_attn, None, None, True, seg, seg.cross_seg,
-                             ln=(x, self.norm2, pos))
+                             ln=(x, self.norm2, pos), record=rec)
         else:
             h = ops.layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, add=pos)
             h0 = None if self.ca_val_has_pos_emb else ops.layernorm(
                 x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
             o = self._attend(self.multihead_attn, h, h0, self.ca_val_has_pos_emb, seg,
-                             seg.cross_seg)
+                             seg.cross_seg, record=rec)
+        if rec is not None:
+            self._store_maps(rec, seg)
         x = linear(o, self.multihead_attn.out_proj.weight, self.multihead_attn.out_proj.bias,
                    residual=x)
         # position-wise feed-forward (:231-238): one launch where supported (ops.ffn: the
@@ -227,19 +283,24 @@ class TransformerCrossEncoderLayer(nn.Module):
             ops.note_state(bound)
         return st[1]
 
-    def _forward_post(self, x, pos, seg: Segments, pending_bias=None):
+    def _forward_post(self, x, pos, seg: Segments, pending_bias=None, record=False):
         """forward_post (transformers.py:109-181): each sub-block's residual sum is formed in
         its output GEMM's epilogue, then LayerNorm'd; the norm1 output is also written with the
         positional embedding added (the cross-attention's q / k input, :139-147). Both
         directions of each attention run in one launch, reading the same pre-update rows
         like the reference's simultaneous src / tgt update."""
         assert pending_bias is None          # only the pre-norm path defers a bias
+        rec = [] if record else None
         h = ops.add(x, pos)                                       # with_pos_embed (:121-124)
-        o = self._attend(self.self_attn, h, x, self.sa_val_has_pos_emb, seg, seg.self_seg)
+        o = self._attend(self.self_attn, h, x, self.sa_val_has_pos_emb, seg, seg.self_seg,
+                         record=rec)
         t = linear(o, self.self_attn.out_proj.weight, self.self_attn.out_proj.bias, residual=x)
         x = ops.layernorm(t, self.norm1.weight, self.norm1.bias, self.norm1.eps)       # :127
         h = ops.layernorm(t, self.norm1.weight, self.norm1.bias, self.norm1.eps, add=pos)
-        o = self._attend(self.multihead_attn, h, x, self.ca_val_has_pos_emb, seg, seg.cross_seg)
+        o = self._attend(self.multihead_attn, h, x, self.ca_val_has_pos_emb, seg, seg.cross_seg,
+                         record=rec)
+        if rec is not None:
+            self._store_maps(rec, seg)
         t = linear(o, self.multihead_attn.out_proj.weight, self.multihead_attn.out_proj.bias,
                    residual=x)
         x = ops.layernorm(t, self.norm2.weight, self.norm2.bias, self.norm2.eps)       # :163
@@ -252,7 +313,18 @@ class TransformerCrossEncoderLayer(nn.Module):
 
 
 class TransformerCrossEncoder(nn.Module):
-    """transformers.py:18-59 with return_intermediate=True semantics."""
+    """transformers.py:18-81 with return_intermediate=True semantics.
+
+    ``record_attention`` (default False): a forward made while it is True also stores every
+    layer's head-averaged attention maps (layer.satt_weights / xatt_weights) for
+    ``get_attentions``. Unlike the reference, which keeps them on every forward, recording is
+    opt-in: the fast forward never forms an attention matrix, so a recording forward takes the
+    route that writes fp32 q / k / v (linear / linear_ln, then ops.attention) and computes the
+    maps from those q / k with a kernel of their own (ops.attention_weights, exact fp32 in
+    either precision mode). Its outputs equal a plain forward's up to rounding. The maps of a
+    padded query row are zero (the reference holds that padded query's softmax there)."""
+
+    record_attention = False
 
     def __init__(self, cross_encoder_layer, num_layers, norm=None, return_intermediate=False):
         super().__init__()
@@ -271,7 +343,8 @@ class TransformerCrossEncoder(nn.Module):
         pending = None
         h1 = side = None
         for l, layer in enumerate(self.layers):
-            x, pending = layer.forward_packed(x, pos, seg, pending, h1=h1, side=side)
+            x, pending = layer.forward_packed(x, pos, seg, pending, h1=h1, side=side,
+                                              record=self.record_attention)
             h1 = side = None
             if self.return_intermediate or l == L - 1:
                 nxt = self.layers[l + 1] if l + 1 < L else None
@@ -289,6 +362,18 @@ class TransformerCrossEncoder(nn.Module):
                     self._norm(x, pending, inter[l if self.return_intermediate else 0])
                 pending = None
         return inter
+
+    def get_attentions(self):
+        """transformers.py:61-81: the maps of the last recording forward, stacked over the
+        layers: ((src_satt, tgt_satt), (src_xatt, tgt_xatt)) of shapes (L, B, Ns, Ns),
+        (L, B, Nt, Nt), (L, B, Ns, Nt), (L, B, Nt, Ns) with Ns / Nt the longest src / tgt
+        cloud. Cross-attention maps are those of the rows before either side's update."""
+        if any(l.satt_weights is None or l.xatt_weights is None for l in self.layers):
+            raise RuntimeError('no attention maps recorded: set record_attention = True and '
+                               'run a forward')
+        satt = tuple(torch.stack([l.satt_weights[s] for l in self.layers]) for s in (0, 1))
+        xatt = tuple(torch.stack([l.xatt_weights[s] for l in self.layers]) for s in (0, 1))
+        return satt, xatt
 
     def _norm(self, x, pending, out):
         if self.norm is None:

@@ -492,6 +492,28 @@ int fgr_attention(const float* q, int64_t ld_q, const float* k, int64_t ld_k, co
                   const int64_t* kv_off, const int32_t* kv_seg, int32_t n_seg,
                   int32_t max_q_len, int32_t n_head, int32_t head_dim, float scale, void* stream);
 
+/* The attention maps nn.MultiheadAttention returns beside its output (need_weights = True, the
+ * default): the post-softmax weights averaged over the heads, which the reference's layers keep
+ * as satt_weights / xatt_weights (transformers.py:177-179, 240-242) for
+ * TransformerCrossEncoder.get_attentions (:61-81). Segments and heads as fgr_attention. For
+ * packed query row r of segment i, n = the length of key segment kv_seg[i]:
+ *   w[r * ld_w + j] = (1 / n_head) sum_h softmax_j(scale q_h[r] . k_h[j])     0 <= j < n
+ *   w[r * ld_w + j] = 0                                                       n <= j < max_kv_len
+ * and columns max_kv_len .. ld_w of a row are not written; an empty query segment writes
+ * nothing (a non-empty one on an empty key segment is outside the contract). An inspection
+ * path, not part of the forward: exact fp32 whatever the precision mode (v_mfma_f32_16x16x4_f32
+ * scores, expf; no f16x3 split, no bf16), every element stored once and no atomics, so two runs
+ * give the same bits. FGR_E_ARG with a message: head_dim not a multiple of 4 or above 256,
+ * ld_w < max_kv_len, ld_q / ld_k < n_head * head_dim, or more heads than the kernel's 64 KiB
+ * of LDS hold the (row, head) softmax statistics of (n_head <= 182 at head_dim >= 32). 16-B
+ * loads / stores where the operand is 16-B aligned with a row stride that is a multiple of 4,
+ * 4-B ones otherwise. No workspace. */
+int fgr_attention_weights(const float* q, int64_t ld_q, const float* k, int64_t ld_k, float* w,
+                          int64_t ld_w, const int64_t* q_off, const int64_t* kv_off,
+                          const int32_t* kv_seg, int32_t n_seg, int32_t max_q_len,
+                          int32_t max_kv_len, int32_t n_head, int32_t head_dim, float scale,
+                          void* stream);
+
 /* fp32-accurate attention on the fp16 matrix cores (head_dim 32 -- ModelNet's d 256 / 8 heads --
  * or 64 -- 3DMatch's d 512 / 8 heads), same semantics and arguments as fgr_attention plus
  * the key segment count / row count / longest key segment and a caller workspace: K/V are

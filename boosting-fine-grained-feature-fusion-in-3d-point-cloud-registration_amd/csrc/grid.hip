@@ -225,96 +225,9 @@ int64_t dense_cap(int64_t n, int64_t max_cells) {
 }
 
 // ------------------------------------------------------------------------------------------
-// radius search over cells
+// radius search over cells (RGrid, its build, cell_coord and dist2g: grid_common.h, shared with
+// icp.hip)
 // ------------------------------------------------------------------------------------------
-struct RGrid {
-    float org[3];
-    float cell;
-    int nx, ny, nz;
-    float radius;                   // the radius the grid was built for (queries use <= it)
-    long long base;                 // first cell counter of the cloud (= 4 s_off[c] + 1024 c)
-};
-
-__host__ __device__ inline long long rgrid_cap(int64_t n_c) { return 4 * n_c + 1024; }
-
-// blocks >= n_clouds zero the cell starts (4096 each), as dgrid_bbox_kernel
-__global__ void __launch_bounds__(1024) rgrid_bbox_kernel(const float* __restrict__ s,
-                                                         const int64_t* __restrict__ s_off,
-                                                         float radius, RGrid* __restrict__ grids,
-                                                         int n_clouds, int* __restrict__ zero,
-                                                         int64_t n_zero) {
-    const int c = blockIdx.x;
-    if (c >= n_clouds) {                                   // block-uniform
-        const int64_t z0 = (int64_t)(c - n_clouds) * 4096;
-        for (int64_t i = z0 + threadIdx.x; i < min(z0 + 4096, n_zero); i += 1024) zero[i] = 0;
-        return;
-    }
-    const int64_t b = s_off[c], e = s_off[c + 1];
-    float mn[3], mx[3];
-    block_bbox(s, b, e, mn, mx);
-    if (threadIdx.x != 0) return;
-    RGrid g;
-    g.radius = radius;
-    g.base = 4 * b + 1024ll * c;
-    if (e <= b) {
-        g.org[0] = g.org[1] = g.org[2] = 0.f;
-        g.cell = radius;
-        g.nx = g.ny = g.nz = 1;
-    } else {
-        const long long cap = rgrid_cap(e - b);
-        float cell = radius * 1.0625f;
-        long long d[3];
-        for (int it = 0; it < 200; ++it) {
-            for (int k = 0; k < 3; ++k) d[k] = (long long)floorf((mx[k] - mn[k]) / cell) + 1;
-            if (d[0] * d[1] * d[2] <= cap && d[0] <= 65536 && d[1] <= 65536 && d[2] <= 65536) break;
-            cell *= 1.25f;
-        }
-        for (int k = 0; k < 3; ++k) g.org[k] = mn[k];
-        g.cell = cell;
-        g.nx = (int)d[0];
-        g.ny = (int)d[1];
-        g.nz = (int)d[2];
-    }
-    grids[c] = g;
-}
-
-__device__ __forceinline__ int cell_coord(float x, float org, float cell) {
-    return (int)floorf((x - org) / cell);
-}
-
-__global__ void rgrid_key_kernel(const float* __restrict__ s, const int64_t* __restrict__ s_off,
-                                 int n_clouds, int64_t ns, const RGrid* __restrict__ grids,
-                                 int* __restrict__ hist, int* __restrict__ cellof,
-                                 int* __restrict__ slot) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ns) return;
-    const int c = find_segment(s_off, n_clouds, i);
-    const RGrid g = grids[c];
-    const int x = min(max(cell_coord(s[3 * i], g.org[0], g.cell), 0), g.nx - 1);
-    const int y = min(max(cell_coord(s[3 * i + 1], g.org[1], g.cell), 0), g.ny - 1);
-    const int z = min(max(cell_coord(s[3 * i + 2], g.org[2], g.cell), 0), g.nz - 1);
-    const int cell = (int)(g.base + ((long long)z * g.ny + y) * g.nx + x);
-    cellof[i] = cell;
-    slot[i] = atomicAdd(&hist[cell], 1);
-}
-
-__global__ void rgrid_scatter_kernel(int64_t ns, const int* __restrict__ cellof,
-                                     const int* __restrict__ slot, const int* __restrict__ start,
-                                     int* __restrict__ members) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ns) return;
-    members[start[cellof[i]] + slot[i]] = (int)i;
-}
-
-// d2 exactly as nanoflann's L2_Simple_Adaptor::evalMetric (and geom.hip's dist2)
-__device__ __forceinline__ float dist2g(float qx, float qy, float qz, float sx, float sy, float sz) {
-    float dx = qx - sx, dy = qy - sy, dz = qz - sz;
-    float d2 = dx * dx;
-    d2 = d2 + dy * dy;
-    d2 = d2 + dz * dz;
-    return d2;
-}
-
 constexpr int kRQ = 4;        // queries (waves) per block
 constexpr int kRCap = 256;    // hits ranked in LDS per query (more: threshold bisection)
 
@@ -440,28 +353,6 @@ rgrid_query_kernel(const float* __restrict__ q, const int64_t* __restrict__ q_of
     for (int k = min(n, width) + lane; k < width; k += 64) row[k] = ns_total;
 }
 
-struct RGridWs {
-    RGrid* grids;
-    int* start;
-    int2* tiles;
-    int *cellof, *slot, *members;
-    size_t total;
-};
-
-void carve_rgrid(void* ws, int64_t ns, int32_t nc, RGridWs* g) {
-    char* p = static_cast<char*>(ws);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { void* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
-    const int64_t cap = 4 * ns + 1024ll * nc;
-    g->grids = (RGrid*)take(sizeof(RGrid) * nc);
-    g->start = (int*)take(4 * (cap + 1));
-    g->tiles = (int2*)take(sizeof(int2) * scan_tiles(cap));
-    g->cellof = (int*)take(4 * ns);
-    g->slot = (int*)take(4 * ns);
-    g->members = (int*)take(4 * ns);
-    g->total = o;
-}
-
 }  // namespace
 }  // namespace fgr
 
@@ -565,24 +456,7 @@ extern "C" int fgr_radius_grid_build(const float* s, const int64_t* s_off, int32
     }
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
-    const int64_t cap = 4 * ns + 1024ll * n_clouds;
-    hipLaunchKernelGGL(rgrid_bbox_kernel, dim3((unsigned)(n_clouds + ceil_div(cap + 1, 4096))),
-                       dim3(1024), 0, st, s, s_off, radius, g.grids, n_clouds, g.start,
-                       (int64_t)(cap + 1));
-    FGR_CHECK_LAUNCH("rgrid_bbox_kernel");
-    if (ns > 0) {
-        hipLaunchKernelGGL(rgrid_key_kernel, dim3((unsigned)ceil_div(ns, 256)), dim3(256), 0, st, s,
-                           s_off, n_clouds, ns, g.grids, g.start, g.cellof, g.slot);
-        FGR_CHECK_LAUNCH("rgrid_key_kernel");
-    }
-    int rc = launch_scan<false>(g.start, nullptr, nullptr, cap, g.tiles, st);
-    if (rc != FGR_OK) return rc;
-    if (ns > 0) {
-        hipLaunchKernelGGL(rgrid_scatter_kernel, dim3((unsigned)ceil_div(ns, 256)), dim3(256), 0,
-                           st, ns, g.cellof, g.slot, g.start, g.members);
-        FGR_CHECK_LAUNCH("rgrid_scatter_kernel");
-    }
-    return FGR_OK;
+    return launch_rgrid_build(s, s_off, n_clouds, ns, radius, g, st);
 }
 
 extern "C" int fgr_radius_search_grid(const float* q, const int64_t* q_off, int32_t n_clouds,

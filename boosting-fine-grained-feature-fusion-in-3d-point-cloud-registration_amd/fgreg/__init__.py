@@ -9,6 +9,8 @@ from .backbone import FixedMetaPreprocessor, KPFEncoder, PreprocessorHIP  # noqa
 from .pose import compute_rigid_transform, fast_compute_rigid_transform  # noqa: F401
 from .regtr import RegTR  # noqa: F401
 from .pipeline import pipeline  # noqa: F401
+from . import refine  # noqa: F401
+from .refine import icp, refine_outputs, score  # noqa: F401
 
 PRECISIONS = ('fp32', 'bf16')
 
@@ -31,4 +33,4 @@ def precision():
 
 __all__ = ['RegTR', 'PreprocessorHIP', 'FixedMetaPreprocessor', 'KPFEncoder', 'ops', 'config',
            'fast_compute_rigid_transform', 'compute_rigid_transform', 'build', 'load', 'FgrError',
-           'set_precision', 'precision']
+           'set_precision', 'precision', 'refine', 'icp', 'score', 'refine_outputs']

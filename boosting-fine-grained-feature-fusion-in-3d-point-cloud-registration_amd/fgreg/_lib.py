@@ -191,6 +191,11 @@ SIGNATURES = {
     'fgr_augment_workspace_bytes': [_i64, _i32, ctypes.POINTER(_sz)],
     'fgr_augment_pairs': [_vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                           _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    'fgr_icp_workspace': [_i64, _i64, _i32, ctypes.POINTER(_sz)],
+    'fgr_icp': [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _f32, _i32, _f32, _f32, _vp, _sz,
+                _vp, _vp, _vp, _vp, _vp],
+    'fgr_registration_score': [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _f32, _vp, _sz,
+                               _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 NB_INDEX, NB_DIST = 0, 1

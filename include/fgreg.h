@@ -987,6 +987,53 @@ int fgr_gemm_f16x3_wgrad(const float* dy, int64_t ld_dy, const float* x, int64_t
                          int64_t rows, int32_t m, int32_t n, float* dw, int64_t ld_dw, float* db,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* ---- pose refinement on the full clouds: point-to-point ICP, fitness, information -------
+ * Not part of the reference: the step its consumers run after the forward (a pose graph over
+ * fragments, RRE / RTE on dense points). Pair b matches source segment b, rows
+ * [src_off[b], src_off[b + 1]) of src (n_src_tot, 3), against target segment b of tgt
+ * (n_tgt_tot, 3); poses are (n_pairs, 3, 4) fp32, source -> target.
+ *
+ * One association pass under a pose T = [R | t]: for every source point p,
+ *   qx = ((R00 px + R01 py) + R02 pz) + tx   (fp32, no FMA; qy, qz likewise),
+ * the nearest target s by d2 = ((qx-sx)^2 + (qy-sy)^2) + (qz-sz)^2 (as fgr_radius_search; the
+ * lowest target row on an exact tie) is its correspondence iff d2 < max_dist * max_dist
+ * (fp32, strict). The targets are binned once per call into the cell grid of
+ * fgr_radius_grid_build at radius max_dist and each query scans the 27 cells around it.
+ * Over the inliers, in fp64 and in a fixed order (no floating-point atomics):
+ *   fitness = n_inl / n_src, rmse = sqrt(sum d2 / n_inl)   (stored as fp32; 0 when n_inl = 0).
+ *
+ * fgr_icp iterates on the device, per pair: pass k = 0, 1, ... associates under T_k and gives
+ * (f_k, e_k). The pair is done when k >= 1 and |f_k - f_(k-1)| < rel_fitness and
+ * |e_k - e_(k-1)| < rel_rmse (fp64), or n_inl < 3, or k == max_iters. Otherwise
+ *   H = sum p s^T - (sum p)(sum s)^T / n_inl, R = V U^T of H's SVD (det +1), t = mean s - R mean p
+ * (p the untransformed source point) becomes T_(k+1), rounded to fp32, and n_iters = k + 1. A
+ * done pair is frozen: pose_out, fitness, rmse (both of pose_out) and n_iters (int32) no longer
+ * change. max_iters + 1 passes are enqueued whatever the data: no readback, allocation or
+ * synchronisation, so a call can be captured into a graph. An empty source or target returns
+ * pose_in, fitness 0, rmse 0, n_iters 0. pose_out must not overlap pose_in.
+ *
+ * fgr_registration_score is one pass under `pose`: fitness, rmse and, each where not NULL,
+ * idx (n_src_tot) int32 = the correspondence's row inside its target segment or -1,
+ * d2 (n_src_tot) fp32 = its d2 or +inf, and info (n_pairs, 6, 6) fp64 =
+ *   sum over the inliers of J^T J, J = [I3 | -[s]x], s the matched target point,
+ * translation first (info[0][0] = n_inl), exactly symmetric.
+ *
+ * Both take fgr_icp_workspace() bytes (the target grid, per-block fp64 partial sums, per-pair
+ * state) and refuse a shorter workspace before anything is launched or written.
+ * 4 n_tgt_tot + 1024 n_pairs and n_src_tot stay below 2^31, n_pairs <= 65535; max_src_len >=
+ * the longest source segment. */
+int fgr_icp_workspace(int64_t n_src_tot, int64_t n_tgt_tot, int32_t n_pairs, size_t* bytes);
+int fgr_icp(const float* src, const int64_t* src_off, int64_t n_src_tot, const float* tgt,
+            const int64_t* tgt_off, int64_t n_tgt_tot, int32_t n_pairs, int32_t max_src_len,
+            const float* pose_in, float max_dist, int32_t max_iters, float rel_fitness,
+            float rel_rmse, void* ws, size_t ws_bytes, float* pose_out, float* fitness,
+            float* rmse, int32_t* n_iters, void* stream);
+int fgr_registration_score(const float* src, const int64_t* src_off, int64_t n_src_tot,
+                           const float* tgt, const int64_t* tgt_off, int64_t n_tgt_tot,
+                           int32_t n_pairs, int32_t max_src_len, const float* pose,
+                           float max_dist, void* ws, size_t ws_bytes, float* fitness, float* rmse,
+                           int32_t* idx, float* d2, double* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,10 @@ SIGNATURES = {
     'fgr_pos_mlp_f16x3_supported': [_i64, _i32],
     'fgr_pos_mlp_f16x3': [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                           _i64, _vp],
+    'fgr_geo_embed_indices': [_vp, _i64, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp],
+    'fgr_geo_embed_f16x3_supported': [_i64, _i32, _i32],
+    'fgr_geo_embed_f16x3': [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64,
+                            _vp],
     'fgr_split_weights_bf16_bytes': [_i32, _i32, ctypes.POINTER(_sz)],
     'fgr_split_weights_bf16': [_vp, _i32, _i32, _i64, _i64, _vp, _vp],
     'fgr_gemm_bf16': [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],

@@ -1196,6 +1196,69 @@ def pos_mlp(xyz, w0, b0, imgs, biases, out=None) -> torch.Tensor:
     return out
 
 
+GEO_MAX, GEO_MEAN = 0, 1        # FGR_GEO_MAX / FGR_GEO_MEAN
+GEO_MAX_K = 4
+
+
+def geo_embed_indices(xyz, cloud_off, k, sigma_d, sigma_a):
+    """GeometricStructureEmbedding.get_embedding_indices (position_embedding.py:145-174) for
+    the k nearest neighbours only (fgr_geo_embed_indices): xyz (n, 3) packed clouds, cloud_off
+    the clouds' device int64 offsets (n_clouds + 1). -> nn (n, k) int32 packed row indices
+    (nearest first, the point itself excluded by index, ties to the lower index), d (n, k) =
+    |p_j - p_i| / sigma_d, a (n, k, k) [i][j][r] = the angle at p_i between p_r and p_j in
+    degrees / sigma_a. Every cloud must have more than k points: the caller checks that on its
+    host lengths (nothing here reads the device table back)."""
+    _dev(xyz, cloud_off)
+    xyz = _c(xyz, torch.float32)
+    cloud_off = _c(cloud_off, torch.int64)
+    n, k = xyz.shape[0], int(k)
+    assert xyz.dim() == 2 and xyz.shape[1] == 3 and cloud_off.dim() == 1
+    if not 1 <= k <= GEO_MAX_K:
+        raise _lib.FgrError(f'geo_embed_indices: k {k} not supported (1..{GEO_MAX_K})')
+    nn = torch.empty((n, k), dtype=torch.int32, device=xyz.device)
+    d = torch.empty((n, k), dtype=torch.float32, device=xyz.device)
+    a = torch.empty((n, k, k), dtype=torch.float32, device=xyz.device)
+    factor_a = 180.0 / (float(sigma_a) * math.pi)
+    _lib.check(_lib.load().fgr_geo_embed_indices(
+        _ptr(xyz), n, _ptr(cloud_off), cloud_off.numel() - 1, k, float(sigma_d), factor_a,
+        _ptr(nn), _ptr(d), _ptr(a), _stream()), 'fgr_geo_embed_indices')
+    return nn, d, a
+
+
+def geo_embed_supported(n, d_model, k) -> bool:
+    """True if the structure embedding's projections and reductions run as one launch
+    (fgr_geo_embed_f16x3: d_model 256, k 1..4)."""
+    return bool(_lib.load().fgr_geo_embed_f16x3_supported(int(n), int(d_model), int(k)))
+
+
+def geo_embed(d, a, div_term, img_d, bias_d, img_a, bias_a, reduction, out=None) -> torch.Tensor:
+    """out[i] = max_j [proj_d(E(d[i, j])) + red_r proj_a(E(a[i, j, r]))] in one launch
+    (fgr_geo_embed_f16x3): d (n, k), a (n, k, k) from geo_embed_indices, div_term (D / 2) the
+    sinusoidal embedding's frequencies, img_* = linear.weight_image(proj_*.weight, mode='f16x3'),
+    reduction GEO_MAX / GEO_MEAN. ``out`` (n, D) may be a row-strided view (stride % 4 == 0,
+    16-B aligned)."""
+    _dev(d, a, div_term, bias_d, bias_a)
+    d, a = _c(d, torch.float32), _c(a, torch.float32)
+    n, k = d.shape
+    assert a.shape == (n, k, k)
+    div_term = _c(div_term, torch.float32)
+    bias_d, bias_a = _c(bias_d, torch.float32), _c(bias_a, torch.float32)
+    D = bias_d.numel()
+    assert bias_a.numel() == D and div_term.numel() * 2 == D
+    assert (img_d.n, img_d.k) == (D, D) and (img_a.n, img_a.k) == (D, D)
+    if out is None:
+        out = torch.empty((n, D), dtype=torch.float32, device=d.device)
+    assert out.shape == (n, D) and out.dtype == torch.float32 and (n == 0 or out.stride(1) == 1)
+    rows = n * k * (1 + k)
+    t0 = _begin('gemm', ('geo_embed', n, D, k))
+    _lib.check(_lib.load().fgr_geo_embed_f16x3(
+        _ptr(d), _ptr(a), n, k, _ptr(div_term), _ptr(img_d.img), _ptr(bias_d), _ptr(img_a.img),
+        _ptr(bias_a), D, int(reduction), _ptr(out),
+        out.stride(0) if n > 1 else max(out.stride(0), D), _stream()), 'fgr_geo_embed_f16x3')
+    _end('gemm', t0, 2 * rows * D * D)
+    return out
+
+
 def corr_head_supported(m, d) -> bool:
     return bool(_lib.load().fgr_corr_head_supported(int(m), int(d)))
 

@@ -24,7 +24,8 @@ from . import linear as lin
 from . import ops
 from .linear import linear
 from .backbone import KPFEncoder, PreprocessorHIP, host_layout
-from .transformer import (PositionEmbeddingCoordsSine, PositionEmbeddingLearned, Segments, TransformerCrossEncoder,
+from .transformer import (GeometricStructureEmbedding, PositionEmbeddingCoordsSine,
+                          PositionEmbeddingLearned, Segments, TransformerCrossEncoder,
                           TransformerCrossEncoderLayer)
 
 _logger = logging.getLogger(__name__)
@@ -242,8 +243,24 @@ class RegTR(nn.Module):
             # finegrained_regtr.py:45-49; the same module object goes to the CorrespondenceDecoder
             # below, so a checkpoint carries the MLP under both prefixes (as the reference's)
             self.pos_embed = PositionEmbeddingLearned(3, cfg.d_embed)
+        elif pos_emb_type == 'geometric':
+            # the reference model has no conf key for it: its forward takes the branch when
+            # ``Geoembeding`` is set on the instance (finegrained_regtr.py:44, :155-161;
+            # INTEGRATION.md). One embedding per cloud there; here all clouds in one call.
+            if (not cfg.get('direct_regress_coor', False)) and cfg.corr_decoder_has_pos_emb:
+                raise NotImplementedError(
+                    "pos_emb_type 'geometric' with the CorrespondenceDecoder head needs "
+                    'corr_decoder_has_pos_emb: False: the reference decoder calls pos_embed on a '
+                    'packed (N, 3) tensor (finegrained_regtr.py:388), which '
+                    'GeometricStructureEmbedding cannot take')
+            opt = {k: cfg[c] for k, c in (('sigma_d', 'geo_sigma_d'), ('sigma_a', 'geo_sigma_a'),
+                                          ('angle_k', 'geo_angle_k'),
+                                          ('reduction_a', 'geo_reduction_a'))
+                   if cfg.get(c) is not None}
+            self.pos_embed = GeometricStructureEmbedding(cfg.d_embed, **opt)
         else:
-            raise NotImplementedError(f"pos_emb_type {pos_emb_type!r}: 'sine' or 'learned'")
+            raise NotImplementedError(
+                f"pos_emb_type {pos_emb_type!r}: 'sine', 'learned' or 'geometric'")
         layer = TransformerCrossEncoderLayer(
             cfg.d_embed, cfg.nhead, cfg.d_feedforward, cfg.dropout,
             activation=cfg.transformer_act, normalize_before=cfg.pre_norm,
@@ -365,7 +382,10 @@ class RegTR(nn.Module):
         feats_un, _ = self.kpf_encoder(feats0, meta)
         both = linear(feats_un, self.feat_proj.weight, self.feat_proj.bias)
         xyz_c = meta['points'][-1]
-        pe = self.pos_embed(xyz_c)
+        if isinstance(self.pos_embed, GeometricStructureEmbedding):
+            pe = self.pos_embed(xyz_c, seg.cloud_off, seg.lengths)
+        else:
+            pe = self.pos_embed(xyz_c)
         pos = pe if self.cfg.transformer_encoder_has_pos_emb else None
         if pos is None:
             pos = torch.zeros_like(both)

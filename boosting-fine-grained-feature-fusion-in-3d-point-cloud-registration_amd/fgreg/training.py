@@ -23,7 +23,7 @@ from .autograd import (attention_t, batchnorm_t, corr_attention_t, kpconv_deform
 from .backbone import (DeformableKPConv, ResnetBottleneckBlock, SimpleBlock, UnaryBlock,
                        _level_inputs, host_layout)
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
-from .transformer import PositionEmbeddingLearned
+from .transformer import GeometricStructureEmbedding, PositionEmbeddingLearned
 
 
 def unary_train(u: UnaryBlock, x, off, lens, residual=None, post_act=ACT_NONE):
@@ -177,6 +177,8 @@ def core_train(model, meta, seg, B):
     xyz_c = meta['points'][-1]
     if isinstance(model.pos_embed, PositionEmbeddingLearned):
         pe = model.pos_embed.train_forward(xyz_c)       # gradients reach the MLP's parameters
+    elif isinstance(model.pos_embed, GeometricStructureEmbedding):
+        pe = model.pos_embed.train_forward(xyz_c, seg.cloud_off, seg.lengths)   # proj_d / proj_a
     else:
         with torch.no_grad():
             pe = model.pos_embed(xyz_c)

@@ -19,6 +19,7 @@ Masked keys never exist, so no -inf masking is needed; padded query rows never e
 so no work is wasted on them.
 """
 import copy
+import math
 
 import torch
 import torch.nn as nn
@@ -455,3 +456,121 @@ class PositionEmbeddingLearned(nn.Module):
             for i, m in enumerate(ls):
                 h = linear_t(h, m.weight, m.bias, act=ops.ACT_RELU if i < 4 else ops.ACT_NONE)
         return h
+
+
+class SinusoidalPositionalEmbedding(nn.Module):
+    """position_embedding.py:102-126: E(t) = [sin(t w_0), cos(t w_0), sin(t w_1), ...] with
+    w_m = exp(-2 m ln(10000) / d_model) kept as the buffer ``div_term`` (so it is in the
+    state_dict, as the reference's)."""
+
+    def __init__(self, d_model):
+        super().__init__()
+        if d_model % 2 != 0:
+            raise ValueError(f'Sinusoidal positional encoding with odd d_model: {d_model}')
+        self.d_model = d_model
+        div_indices = torch.arange(0, d_model, 2).float()
+        self.register_buffer('div_term', torch.exp(div_indices * (-math.log(10000.0) / d_model)))
+
+    def forward(self, emb_indices):
+        """(*) -> (*, d_model), detached, in torch ops (the composed and training paths; the
+        fused kernel builds the same rows on chip)."""
+        omegas = emb_indices.reshape(-1, 1) * self.div_term.view(1, -1)
+        emb = torch.stack([torch.sin(omegas), torch.cos(omegas)], dim=2)
+        return emb.view(*emb_indices.shape, self.d_model).detach()
+
+
+class GeometricStructureEmbedding(nn.Module):
+    """position_embedding.py:129-196 (``pos_emb_type: geometric``): per point, the
+    rotation-invariant embedding of its distances and angles to its ``angle_k`` nearest
+    neighbours of the same cloud. With k = angle_k, D = hidden_dim and nn(i) the k nearest
+    OTHER points of point i's cloud,
+
+        d_ij  = |p_j - p_i| / sigma_d                                         j in nn(i)
+        a_ijr = atan2(|(p_r - p_i) x (p_j - p_i)|, (p_r - p_i) . (p_j - p_i))
+                * 180 / (sigma_a pi)                                          j, r in nn(i)
+        out_i = max_j [ proj_d(E(d_ij)) + red_r proj_a(E(a_ijr)) ]
+
+    with E the interleaved sinusoidal embedding (SinusoidalPositionalEmbedding), red = max or
+    mean (``reduction_a``) and both maxima per channel; r = j stays in (angle 0), as in the
+    reference. State_dict layout of the reference: ``embedding.div_term`` (buffer),
+    ``proj_d.{weight,bias}``, ``proj_a.{weight,bias}``.
+
+    The reference embeds every pair and triplet of a cloud ((1, N, N, k, D) tensors) and then
+    gathers the k nearest columns; only the k (1 + k) rows per point that survive the gather are
+    computed here. Two deliberate differences, which agree with the reference wherever a cloud
+    has no duplicate points (grid subsampling guarantees that):
+
+    * distances come from coordinate differences, not from x^2 - 2 x.y + y^2 in fp32 (clamped at
+      0), whose cancellation error reaches the distance itself at 3DMatch scale (x^2 ~ 16,
+      d^2 ~ 0.01); ours is the more accurate form;
+    * the point itself is excluded by index, not by dropping the first of the k + 1 smallest;
+      ties in squared distance go to the lower index.
+
+    A cloud with n <= k points makes the reference's topk raise; forward raises ValueError from
+    the host lengths before anything is launched.
+
+    forward(xyz, cloud_off, lengths): xyz (N, 3) the packed clouds, cloud_off their device
+    offsets (Segments.cloud_off), lengths the host lengths. Two launches where
+    ops.geo_embed_supported (fgr_geo_embed_indices, fgr_geo_embed_f16x3), else forward_composed.
+    Always f16x3, in both precision modes, like the other two embeddings. No host sync, so it
+    runs inside the captured core graph. train_forward is differentiable in proj_d / proj_a."""
+
+    def __init__(self, hidden_dim, sigma_d=0.2, sigma_a=15, angle_k=3, reduction_a='max'):
+        super().__init__()
+        self.sigma_d = sigma_d
+        self.sigma_a = sigma_a
+        self.factor_a = 180.0 / (self.sigma_a * math.pi)
+        self.angle_k = angle_k
+        self.hidden_dim = hidden_dim
+        self.embedding = SinusoidalPositionalEmbedding(hidden_dim)
+        self.proj_d = nn.Linear(hidden_dim, hidden_dim)
+        self.proj_a = nn.Linear(hidden_dim, hidden_dim)
+        self.reduction_a = reduction_a
+        if self.reduction_a not in ['max', 'mean']:
+            raise ValueError(f'Unsupported reduction mode: {self.reduction_a}.')
+
+    def _indices(self, xyz, cloud_off, lengths):
+        k = self.angle_k
+        short = [int(n) for n in lengths if int(n) <= k]
+        if short:
+            raise ValueError(f'GeometricStructureEmbedding: a cloud of {short[0]} points has no '
+                             f'{k} nearest neighbours (angle_k {k} needs more than {k} points)')
+        if sum(int(n) for n in lengths) != xyz.shape[0]:
+            raise ValueError('GeometricStructureEmbedding: lengths do not sum to the rows of xyz')
+        with torch.no_grad():
+            return ops.geo_embed_indices(xyz, cloud_off, k, self.sigma_d, self.sigma_a)
+
+    def forward(self, xyz, cloud_off, lengths):
+        k, D = self.angle_k, self.hidden_dim
+        if not ops.geo_embed_supported(max(xyz.shape[0], 1), D, k):
+            return self.forward_composed(xyz, cloud_off, lengths)
+        _, d, a = self._indices(xyz, cloud_off, lengths)
+        return ops.geo_embed(d, a, self.embedding.div_term,
+                             lin.weight_image(self.proj_d.weight, mode='f16x3'), self.proj_d.bias,
+                             lin.weight_image(self.proj_a.weight, mode='f16x3'), self.proj_a.bias,
+                             ops.GEO_MEAN if self.reduction_a == 'mean' else ops.GEO_MAX)
+
+    def _reduce(self, pd, pa, n):
+        k, D = self.angle_k, self.hidden_dim
+        pa = pa.view(n, k, k, D)
+        pa = pa.max(dim=2)[0] if self.reduction_a == 'max' else pa.mean(dim=2)
+        return (pd.view(n, k, D) + pa).max(dim=1)[0]
+
+    def forward_composed(self, xyz, cloud_off, lengths):
+        """The same embedding from the indices kernel, torch sin / cos, two linear() launches and
+        torch reductions (the path for shapes the fused kernel refuses, and its A/B baseline)."""
+        _, d, a = self._indices(xyz, cloud_off, lengths)
+        with lin.mode_scope('f16x3'):
+            pd = linear(self.embedding(d.reshape(-1)), self.proj_d.weight, self.proj_d.bias)
+            pa = linear(self.embedding(a.reshape(-1)), self.proj_a.weight, self.proj_a.bias)
+        return self._reduce(pd, pa, xyz.shape[0])
+
+    def train_forward(self, xyz, cloud_off, lengths):
+        """Differentiable forward: the indices without gradients and E detached, as in the
+        reference; two autograd.linear_t calls (f16x3) and torch reductions."""
+        from .autograd import linear_t
+        _, d, a = self._indices(xyz, cloud_off, lengths)
+        with lin.mode_scope('f16x3'):
+            pd = linear_t(self.embedding(d.reshape(-1)), self.proj_d.weight, self.proj_d.bias)
+            pa = linear_t(self.embedding(a.reshape(-1)), self.proj_a.weight, self.proj_a.bias)
+        return self._reduce(pd, pa, xyz.shape[0])

@@ -471,6 +471,42 @@ int fgr_pos_mlp_f16x3(const float* xyz, int64_t n, const float* w0, const float*
                       const void* w3_img, const float* b3, const void* w4_img, const float* b4,
                       int32_t d_model, float* out, int64_t ldo, void* stream);
 
+/* GeometricStructureEmbedding (position_embedding.py:129-196) in two launches. For point i of a
+ * cloud, nn(i) = its k nearest OTHER points of the same cloud (squared distance from coordinate
+ * differences in fp32; i excluded by index; ties to the lower index),
+ *   d_ij  = |p_j - p_i| / sigma_d                                              j in nn(i)
+ *   a_ijr = atan2(|(p_r - p_i) x (p_j - p_i)|, (p_r - p_i) . (p_j - p_i)) * factor_a,  j, r in nn(i)
+ *   E(t)  = [sin(t w_0), cos(t w_0), sin(t w_1), cos(t w_1), ...]   (d_model values)
+ *   out_i = max_j [ proj_d(E(d_ij)) + red_r proj_a(E(a_ijr)) ],  red = max | mean, per channel.
+ *
+ * fgr_geo_embed_indices: xyz (n, 3) contiguous fp32, the clouds packed end to end; cloud_off
+ * (n_clouds + 1) int64 DEVICE row offsets, cloud_off[0] = 0, cloud_off[n_clouds] = n. Writes nn
+ * (n, k) int32 (packed row indices, nearest first), d (n, k), a (n, k, k) [i][j][r] fp32, exactly
+ * those elements. k 1..4. A cloud must have more than k points; that is the CALLER's check (the
+ * table is on the device): in a shorter cloud the missing neighbours are the point itself (d 0,
+ * a 0), never a row of another cloud or out of bounds. factor_a = 180 / (sigma_a pi). Precise
+ * sqrtf / atan2f, no atomics, deterministic. No workspace.
+ *
+ * fgr_geo_embed_f16x3: d, a as written above; div_term (d_model / 2) fp32 = w_m; wd_img / wa_img
+ * = fgr_split_weights_h3 of proj_d.weight / proj_a.weight (d_model, d_model); bd / ba the raw
+ * fp32 biases; reduction FGR_GEO_MAX / FGR_GEO_MEAN; out (n, d_model) with row stride ldo. The
+ * k (1 + k) embedding rows of a point are built on chip (precise sinf / cosf) and never reach
+ * memory; the projections are the f16x3 products of fgr_gemm_f16x3. A point's result depends on
+ * its own d / a values alone, bit for bit. Images, biases, div_term and out 16-B aligned, ldo >=
+ * d_model, ldo % 4 == 0; out[i][d_model .. ldo) is not written. No workspace.
+ * fgr_geo_embed_f16x3_supported(n, d_model, k): n >= 1, d_model 256, k 1..4; anything else is
+ * FGR_E_ARG with a message; n = 0 returns FGR_OK and touches nothing. */
+#define FGR_GEO_MAX 0
+#define FGR_GEO_MEAN 1
+int fgr_geo_embed_indices(const float* xyz, int64_t n, const int64_t* cloud_off, int32_t n_clouds,
+                          int32_t k, float sigma_d, float factor_a, int32_t* nn, float* d,
+                          float* a, void* stream);
+int fgr_geo_embed_f16x3_supported(int64_t n, int32_t d_model, int32_t k);
+int fgr_geo_embed_f16x3(const float* d, const float* a, int64_t n, int32_t k,
+                        const float* div_term, const void* wd_img, const float* bd,
+                        const void* wa_img, const float* ba, int32_t d_model, int32_t reduction,
+                        float* out, int64_t ldo, void* stream);
+
 int fgr_split_weights_bf16_bytes(int32_t n, int32_t k, size_t* bytes);
 int fgr_split_weights_bf16(const float* w, int32_t n, int32_t k, int64_t stride_n,
                            int64_t stride_k, void* img, void* stream);

@@ -1070,6 +1070,53 @@ int fgr_registration_score(const float* src, const int64_t* src_off, int64_t n_s
                            float max_dist, void* ws, size_t ws_bytes, float* fitness, float* rmse,
                            int32_t* idx, float* d2, double* info, void* stream);
 
+/* ---- robust pose: RANSAC over putative correspondences -----------------------------------
+ * The estimator between the forward's correspondences and fgr_icp (the reference ships an
+ * unreachable one, models/ransaclib; this is not a port of it). a, b are (n_tot, 3) packed
+ * correspondences with b ~ R a + t, w (n_tot) their weights or NULL, off (n_pairs + 1) device
+ * row offsets; pair p owns rows [off[p], off[p + 1]).
+ *
+ * Eligibility: row i is eligible iff w == NULL or w[i] > w_min (strict; a NaN weight is not).
+ *   m = n_eligible[p]; the eligible rows keep their order, a rank is a position in that order.
+ * Sampling: hypothesis h of pair p draws the ranks
+ *   r_k = ((uint64) hash(seed, k, p, h) * m) >> 32,  k = 0, 1, 2,
+ *   hash = the counter-based hash of the attention dropout (csrc/common.h attn_drop_hash with
+ *   head = k, q = p, k = h; restated by fgreg.autograd). Two equal ranks, or m < 3, make the
+ *   hypothesis invalid: hyp_count = -1, hyp_pose = identity, it never wins.
+ * Minimal solve, fp64: centroids am = ((a0 + a1) + a2) / 3 and bm, H = sum (a - am)(b - bm)^T,
+ *   R = V U^T of H's SVD with the reflection fix (det +1), t = bm - R am, rounded once to an
+ *   fp32 (3, 4) pose. A collinear sample is valid and gets one of the optimal rotations, as
+ *   fgr_procrustes.
+ * Score: the number of eligible rows with d2 < r2, all fp32 without FMA,
+ *   qx = ((R00 x + R01 y) + R02 z) + tx (qy, qz likewise), d = q - b,
+ *   d2 = ((dx dx) + dy dy) + dz dz, r2 = inlier_dist * inlier_dist (as fgr_icp's pass).
+ * Selection: the largest count wins, ties go to the lowest h -> best_hyp. Without a valid
+ *   hypothesis: best_hyp = -1, pose = identity, n_inliers = 0, inlier_rmse = 0, n_updates = 0,
+ *   mask all 0.
+ * Refits, at most n_refits, from the winner (T, c): K = {eligible i : d2_T(i) < r2}; stop if
+ *   |K| < 3; T' = the fp64 unweighted Kabsch over K (sums in a fixed order, no floating-point
+ *   atomics) rounded to fp32; c' = the count under T'; if c' < c stop and keep T; otherwise
+ *   adopt T' and ++n_updates; if c' == c stop, else c = c' and repeat.
+ * Outputs, under the final T: pose (n_pairs, 3, 4), n_inliers, inlier_rmse =
+ *   fp32(sqrt(sum d2 / n_inliers)) with the sum in fp64 (0 without inliers), n_eligible,
+ *   best_hyp, n_updates (all (n_pairs), int32 but the rmse); each where not NULL: inlier_mask
+ *   (n_tot) in the caller's row order, 1 = inlier, 0 otherwise and for ineligible rows;
+ *   hyp_pose (n_pairs, n_hyp, 3, 4) and hyp_count (n_pairs, n_hyp), every hypothesis's pose
+ *   and score.
+ * FGR_E_ARG, with nothing launched or written: n_pairs outside 1..65535, n_hyp outside
+ * 1..2^20, n_refits < 0, inlier_dist not finite or <= 0, n_tot outside 0..2^31 - 1, a NULL
+ * required pointer (a, b may be NULL when n_tot == 0), ws not 16-B aligned, ws_bytes below
+ * fgr_ransac_workspace() (the compacted rows and one 64-B slot per 256 hypotheses and pair;
+ * exactly the bytes used). Three launches on `stream`, whatever the data: no readback,
+ * allocation or synchronisation, so a call can be captured into a graph. */
+int fgr_ransac_workspace(int64_t n_tot, int32_t n_pairs, int32_t n_hyp, size_t* bytes);
+int fgr_ransac_pose(const float* a, const float* b, const float* w, int64_t n_tot,
+                    const int64_t* off, int32_t n_pairs, float w_min, float inlier_dist,
+                    int32_t n_hyp, uint32_t seed, int32_t n_refits, void* ws, size_t ws_bytes,
+                    float* pose, int32_t* n_inliers, float* inlier_rmse, int32_t* n_eligible,
+                    int32_t* best_hyp, int32_t* n_updates, uint8_t* inlier_mask, float* hyp_pose,
+                    int32_t* hyp_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,39 +22,16 @@
 // so every softmax row is lane-local; 16x16x32 f16 lane maps (lane l, g = l >> 4,
 // c = l & 15): A[i = c][k = 8g + e], B[k = 8g + e][j = c], C[i = 4g + r][j = c].
 // Per-(tile, head) image, 256 * DH B (16 KB at DH 32, 32 KB at DH 64), staged into LDS by a
-// flat copy:
-//   K: [k-step DH/32][term 2][g 4][key 64] x 16 B (8 dims)   ds_read_b128, conflict-free
-//   V: [term 2][key 64][DH] f16, 16-B chunk index XOR v_swz<DH>(key)
-// Tile t of kv segment s sits at tile index kv_off[s] / 64 + s + t; the (e_k, e_v) scale
-// exponents of all tiles follow the images.
+// flat copy: KvImage<DH, 2> (attn_tile.h). Tile t of kv segment s sits at tile index
+// seg_tile(kv_off[s], s) + t; the (e_k, e_v) scale exponents of all tiles follow the images.
 #include <algorithm>
-#include <type_traits>
 
-#include "mfma.h"
+#include "attn_tile.h"
 
 namespace fgr {
 namespace {
 
-// 16-B units per (tile, head) image and the first V unit, by head dim
-template <int DH> constexpr int units() { return DH * 16 + (DH / 32) * 512; }
-template <int DH> constexpr int unit_v() { return (DH / 32) * 512; }
-
-__device__ __forceinline__ void split2(float x, _Float16& h, _Float16& m) {
-    h = (_Float16)x;
-    m = (_Float16)(x - (float)h);
-}
-
-// V image row swizzle: XOR applied to the 16-B chunk index of key row `key`, so that the
-// ds_read_b64_tr_b16 of a 32-lane group (8 key rows x 32 B) hits 64 distinct banks. DH 32
-// (64-B rows, 4 per 256-B bank period): rows r, r + 4 separated by 32 B (row bit 2); DH 64
-// (128-B rows, 2 per period): rows r, r + 2, r + 4, r + 6 share banks and take four distinct
-// 32-B chunk pairs (row bits 1-2) -- without it they read 2-way conflicted (round-3 PMC:
-// 1.2 M conflict cycles per 0.9 M LDS instructions at DH 64, none at DH 32).
-template <int DH>
-__device__ __forceinline__ int v_swz(int key) {
-    if constexpr (DH == 64) return ((key >> 1) & 3) << 1;
-    else return ((key >> 2) & 1) << 1;
-}
+template <int DH> using Img16 = KvImage<DH, 2>;
 
 template <int DH>
 __device__ __forceinline__ void kv_image16(const float* __restrict__ k, int64_t ld_k,
@@ -68,8 +45,8 @@ __device__ __forceinline__ void kv_image16(const float* __restrict__ k, int64_t 
     const int nk = (int)(kv_off[s + 1] - kb);
     if (tt * 64 >= nk) return;                                   // block-uniform
     __shared__ float red[2][4];
-    const int64_t tile = (kb / 64 + s + tt) * n_head + h;
-    char* base = reinterpret_cast<char*>(img + tile * units<DH>());
+    const int64_t tile = (seg_tile(kb, s) + tt) * n_head + h;
+    char* base = reinterpret_cast<char*>(img + tile * Img16<DH>::units);
     float kf[NF][4], vf[NF][4];
     float km = 0.f, vm = 0.f;
 #pragma unroll
@@ -113,14 +90,12 @@ __device__ __forceinline__ void kv_image16(const float* __restrict__ k, int64_t 
             split2(vf[i][j] * sv, vt[0][j], vt[1][j]);
         }
         const int ks = d0 >> 5, g = (d0 & 31) >> 3, half = (d0 >> 2) & 1;
-        const int vch = (d0 >> 3) ^ v_swz<DH>(key);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            *reinterpret_cast<uint2*>(base + (((ks * 2 + t) * 4 + g) * 64 + key) * 16 + half * 8) =
+            *reinterpret_cast<uint2*>(base + Img16<DH>::k_unit(ks, t, g, key) + half * 8) =
                 *reinterpret_cast<const uint2*>(kt[t]);
             if (v_part)
-                *reinterpret_cast<uint2*>(base + unit_v<DH>() * 16 + t * (128 * DH) + key * (2 * DH) +
-                                          vch * 16 + half * 8) =
+                *reinterpret_cast<uint2*>(Img16<DH>::v_chunk_at(base, t, key, d0 >> 3) + half * 8) =
                     *reinterpret_cast<const uint2*>(vt[t]);
         }
     }
@@ -209,14 +184,13 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
                      float scale_log2, int global_tiles, uint32_t drop_seed = 0,
                      uint32_t drop_thresh = 0, float inv_keep = 1.f, float* __restrict__ lse_out = nullptr) {
     constexpr int KD = DH / 32, TD = DH / 16;
-    constexpr int UN = units<DH>();
+    constexpr int UN = Img16<DH>::units;
     constexpr int PW = UN / 64 / 4;                              // DMA pieces per wave per tile
     // the two K/V tile buffers as two LDS objects, addressed by pointers derived from them:
     // the compiler's LDS-DMA tracking then knows that the DMA filling one buffer cannot alias
     // reads of the other (one array + integer addresses made it wait for the in-flight DMA of
     // the next tile -- vmcnt(0) -- before the first V read of every tile)
     __shared__ u32x4 lds_b0[UN], lds_b1[UN];
-    typedef __attribute__((address_space(3))) char lds_c;
     const int L = blockIdx.x, xcd = L & 7, j0 = L >> 3;
     const int pair = (j0 / n_qblk) * 8 + xcd, qblk = j0 % n_qblk;
     if (pair >= n_seg * n_head) return;
@@ -232,7 +206,7 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
     // segment's keys then start `lead` rows into its first tile
     const int lead = global_tiles ? (int)(kb & 63) : 0;
     const int ntile = (lead + nk + 63) / 64;
-    const int64_t tile0 = (global_tiles ? kb / 64 : kb / 64 + ks) * n_head + head;
+    const int64_t tile0 = (global_tiles ? global_tile(kb) : seg_tile(kb, ks)) * n_head + head;
     const int64_t tile_stride = (int64_t)n_head * UN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
@@ -277,61 +251,31 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
     float m_run = -INFINITY, l_run = 0.f;
     const float one = 1.0f;
 
-    // per-lane LDS byte addresses (buffer 0); everything else is an instruction offset
-    const uint32_t kaddr = (uint32_t)(g * 64 + c) * 16;            // K fragment reads (bytes)
-    // V transposed reads: lane c = 4qq + p reads rows 4g + qq (+16 k, +32 j), columns
-    // 16t + 4p .. +3: chunk 2t + (p >> 1) XOR the image's row swizzle (v_swz)
-    const int qq = c >> 2, pp = c & 3;
+    const uint32_t kaddr = k_frag_addr(g, c);
     uint32_t vaddr[TD];
 #pragma unroll
-    for (int t = 0; t < TD; ++t)
-        vaddr[t] = unit_v<DH>() * 16 + (4 * g + qq) * (2 * DH) +
-                   (((2 * t + (pp >> 1)) ^ v_swz<DH>(4 * g + qq)) * 16) + (pp & 1) * 8;
+    for (int t = 0; t < TD; ++t) vaddr[t] = v_tr_addr<DH, 2>(g, c, t);
 
     auto dma = [&](int t, auto buf_tag) {                        // tile t -> buffer BUF
         constexpr int BUF = decltype(buf_tag)::value;
-        const u32x4* src = src_lane + (int64_t)t * tile_stride;
-        __attribute__((address_space(3))) char* dst =
-            (lds_c*)(BUF == 0 ? lds_b0 : lds_b1) + wv * PW * 1024;
-#pragma unroll
-        for (int j = 0; j < PW; ++j)
-            __builtin_amdgcn_global_load_lds((const void*)(src + j * 64),
-                                             (__attribute__((address_space(3))) void*)(dst + j * 1024),
-                                             16, 0, 0);
+        dma_pieces<PW>(src_lane + (int64_t)t * tile_stride,
+                       (lds_c*)(BUF == 0 ? lds_b0 : lds_b1) + wv * PW * 1024);
     };
-    // tile tt lives in LDS buffer (tt + shift) & 1: a masked first tile (lead > 0) takes buffer 1
-    // so that the unrolled pairs of full tiles always start on buffer 0
-    const int shift = lead > 0 ? 1 : 0;
-    if (ntile > 0) {
-        if (shift) dma(0, std::integral_constant<int, 1>{});
-        else dma(0, std::integral_constant<int, 0>{});
-    }
-
     auto tile = [&](int tt, auto buf_tag, auto mask_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool MASK = decltype(mask_tag)::value;
-        wait_vm_lgkm0<0>();           // this wave's pieces of tile tt landed
-        __builtin_amdgcn_s_barrier();   // everyone's landed; buffer 1 - BUF no longer read
-        if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
+        tile_enter<BUF>(tt, ntile, dma);
         const int2 e2 = sc[tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head];
         lds_c* const bp = (lds_c*)(BUF == 0 ? lds_b0 : lds_b1);
-        typedef __attribute__((address_space(3))) u32x4 lds_u4;
-        typedef __attribute__((address_space(3))) s16x4 lds_s4;
 
         f32x4 s[4];
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int kd = 0; kd < KD; ++kd) {
-                const f16x8 kh = __builtin_bit_cast(
-                    f16x8, *(lds_u4*)(bp + kaddr + (((kd * 2 + 0) * 4) * 64 + 16 * n) * 16));
-                const f16x8 kl = __builtin_bit_cast(
-                    f16x8, *(lds_u4*)(bp + kaddr + (((kd * 2 + 1) * 4) * 64 + 16 * n) * 16));
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qt[kd][0], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qt[kd][1], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qt[kd][0], a, 0, 0, 0);
-            }
+            for (int kd = 0; kd < KD; ++kd)
+                mma_h3(read_k_frag<f16x8, DH, 2>(bp, kaddr, kd, 0, n),
+                       read_k_frag<f16x8, DH, 2>(bp, kaddr, kd, 1, n), qt[kd][0], qt[kd][1], a);
             s[n] = a;
         }
         const float f = __builtin_ldexpf(1.f, -(e2.x + eq));
@@ -388,18 +332,8 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
 #pragma unroll
             for (int t = 0; t < TD; ++t) {
                 f16x8 vf[2];
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) {
-                    lds_c* const vb = bp + vaddr[t] + tm * (128 * DH) + j * 32 * (2 * DH);
-                    const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)vb);
-                    const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vb + 16 * (2 * DH)));
-                    vf[tm] = __builtin_bit_cast(f16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
-                }
-                f32x4 a = tmp[t];
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[1], pt0, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[0], pt1, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[0], pt0, a, 0, 0, 0);
-                tmp[t] = a;
+                read_v_tr2<DH>(bp + vaddr[t] + j * 32 * (2 * DH), vf);
+                mma_h3(vf[0], vf[1], pt0, pt1, tmp[t]);
             }
         }
         const float fv = __builtin_ldexpf(1.f, -e2.y);   // p14's 2^14 cancels against l's
@@ -408,8 +342,15 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[t][r] = __builtin_fmaf(tmp[t][r], fv, acc[t][r] * alpha);
     };
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
+    // tile tt lives in LDS buffer (tt + shift) & 1: a masked first tile (lead > 0) takes buffer 1
+    // so that the unrolled pairs of full tiles always start on buffer 0. This loop stays in the
+    // kernel (and in attn_bf16_v2_kernel): as a function of attn_tile.h the compiler merged the
+    // tails of the last tile's two copies and loaded the merged tail's e_v late
+    const int shift = lead > 0 ? 1 : 0;
+    if (ntile > 0) {
+        if (shift) dma(0, B1{});
+        else dma(0, B0{});
+    }
     const int nfull = (lead + nk) / 64;              // tiles [shift, nfull) have 64 valid keys
     int tt = 0;
     if (shift) {                                     // the first tile, keys before the segment masked
@@ -447,8 +388,6 @@ attn_f16x3_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __r
     }
 }
 
-int64_t n_tiles16(int64_t n_kv_rows, int32_t n_kv_seg) { return n_kv_rows / 64 + n_kv_seg + 1; }
-
 // ---- training: dQ of the attention on the f16 matrix cores (f16x3), given the forward's
 // log2-sum-exp (fgr_attention_bwd_train). The forward kernel's structure with three images per
 // 64-key tile, built by attn_kv_image16_kernel (per-segment tiles):
@@ -459,6 +398,16 @@ int64_t n_tiles16(int64_t n_kv_rows, int32_t n_kv_seg) { return n_kv_rows / 64 +
 //   dQ^T[dh][query] += K^T dS^T     A = K (imgK, V part: transposed reads), B = dS (registers,
 //                                   per query and tile scaled into fp16's range and split)
 // dQ = scale * sum dS K. Same lane maps, DMA double buffer and barriers as the forward.
+// a . b over a lane's 8 dims as four pair sums, the contraction of each pair written out (one
+// product rounded, the other fused onto it): left to the compiler, a0 b0 + a1 b1 fuses either
+// product, which one depends on the code around it, and D's last bit with it. Which product of
+// each pair is the rounded one (0, 3, 4, 6) has no other reason than that the compiler chose so
+// when the kernel loaded its rows inline: dq and dk keep those bits ("Same bits")
+__device__ __forceinline__ float dot8_pairs(const float (&a)[8], const float (&b)[8]) {
+    return (__builtin_fmaf(a[1], b[1], a[0] * b[0]) + __builtin_fmaf(a[2], b[2], a[3] * b[3])) +
+           (__builtin_fmaf(a[5], b[5], a[4] * b[4]) + __builtin_fmaf(a[7], b[7], a[6] * b[6]));
+}
+
 template <int DH, bool DROP>
 __global__ void __launch_bounds__(256, DH == 64 ? 2 : 4)
 attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float* __restrict__ dout,
@@ -472,15 +421,12 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
                          float* __restrict__ dsum_out, float* __restrict__ lsed_t,
                          uint32_t drop_seed, uint32_t drop_thresh, float inv_keep) {
     constexpr int KD = DH / 32, TD = DH / 16;
-    constexpr int UN = units<DH>();                              // imgK units per tile
-    constexpr int UK = unit_v<DH>();                             // the K part (imgV)
+    constexpr int UN = Img16<DH>::units;                         // imgK units per tile
+    constexpr int UK = Img16<DH>::unit_v;                        // the K part (imgV)
     constexpr int PW = UN / 64 / 4, PWV = UK / 64 / 4;           // DMA pieces per wave per tile
     __shared__ u32x4 lk0[UN], lk1[UN], lv0[UK], lv1[UK];
-    typedef __attribute__((address_space(3))) char lds_c;
-    const int L = blockIdx.x, xcd = L & 7, j0 = L >> 3;
-    const int pair = (j0 / n_qblk) * 8 + xcd, qblk = j0 % n_qblk;
-    if (pair >= n_seg * n_head) return;
-    const int seg = pair / n_head, head = pair % n_head;
+    int seg, head, qblk;
+    if (!block_split(n_qblk, n_seg, n_head, seg, head, qblk)) return;
     const int64_t qb = q_off[seg], qe = q_off[seg + 1];
     const int64_t q0 = qb + (int64_t)qblk * 64;
     if (q0 >= qe) return;                                        // block-uniform
@@ -488,7 +434,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
     const int64_t kb = kv_off[ks];
     const int nk = (int)(kv_off[ks + 1] - kb);
     const int ntile = (nk + 63) / 64;
-    const int64_t tile0 = (kb / 64 + ks) * n_head + head;
+    const int64_t tile0 = seg_tile(kb, ks) * n_head + head;
     const int64_t tile_stride_k = (int64_t)n_head * UN, tile_stride_v = (int64_t)n_head * UN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
@@ -498,106 +444,52 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
     // this lane's query row: q (scaled into the log2 domain), dO, and D = dO . O
     const int64_t qrow = q0 + wv * 16 + c;
     const bool qok = qrow < qe;
-    float x[KD][8], y[KD][8];
+    float x[KD][8], y[KD][8], z[KD][8];
+    load_row8<KD>(q + qrow * ld_q + head * DH + 8 * g, qok, x);
+    load_row8<KD>(dout + qrow * ld_do + head * DH + 8 * g, qok, y);
+    load_row8<KD>(o + qrow * ld_o + head * DH + 8 * g, qok, z);
     float dpart = 0.f;
 #pragma unroll
-    for (int kd = 0; kd < KD; ++kd) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, da = a, db = a, oa = a, ob = a;
-        if (qok) {
-            const int64_t col = head * DH + 32 * kd + 8 * g;
-            const float4* pq = reinterpret_cast<const float4*>(q + qrow * ld_q + col);
-            const float4* pd = reinterpret_cast<const float4*>(dout + qrow * ld_do + col);
-            const float4* po = reinterpret_cast<const float4*>(o + qrow * ld_o + col);
-            a = pq[0]; b = pq[1]; da = pd[0]; db = pd[1]; oa = po[0]; ob = po[1];
-        }
-        x[kd][0] = a.x; x[kd][1] = a.y; x[kd][2] = a.z; x[kd][3] = a.w;
-        x[kd][4] = b.x; x[kd][5] = b.y; x[kd][6] = b.z; x[kd][7] = b.w;
-        y[kd][0] = da.x; y[kd][1] = da.y; y[kd][2] = da.z; y[kd][3] = da.w;
-        y[kd][4] = db.x; y[kd][5] = db.y; y[kd][6] = db.z; y[kd][7] = db.w;
-        dpart += ((da.x * oa.x + da.y * oa.y) + (da.z * oa.z + da.w * oa.w)) +
-                 ((db.x * ob.x + db.y * ob.y) + (db.z * ob.z + db.w * ob.w));
-    }
+    for (int kd = 0; kd < KD; ++kd) dpart += dot8_pairs(y[kd], z[kd]);
     const float D = xg_sum(dpart);
     const float lse2 = qok ? lse_in[qrow * n_head + head] : 0.f;
-    float qm = 0.f, dm = 0.f;
-#pragma unroll
-    for (int kd = 0; kd < KD; ++kd)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            x[kd][e] *= scale_log2;
-            qm = fmaxf(qm, fabsf(x[kd][e]));
-            dm = fmaxf(dm, fabsf(y[kd][e]));
-        }
-    const int eq = row_scale_exp(xg_max(qm)), edo = row_scale_exp(xg_max(dm));
-    const float sq = __builtin_ldexpf(1.f, eq), sdo = __builtin_ldexpf(1.f, edo);
     f16x8 qt[KD][2], dt[KD][2];
-#pragma unroll
-    for (int kd = 0; kd < KD; ++kd)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            _Float16 h, m;
-            split2(x[kd][e] * sq, h, m);
-            qt[kd][0][e] = h; qt[kd][1][e] = m;
-            split2(y[kd][e] * sdo, h, m);
-            dt[kd][0][e] = h; dt[kd][1][e] = m;
-        }
+    const int eq = split_row8<KD>(x, scale_log2, qt), edo = split_row8<KD>(y, 1.f, dt);
     f32x4 acc[TD];
 #pragma unroll
     for (int t = 0; t < TD; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float one = 1.0f;
-    const uint32_t kaddr = (uint32_t)(g * 64 + c) * 16;
-    const int qq = c >> 2, pp = c & 3;
+    const uint32_t kaddr = k_frag_addr(g, c);
     uint32_t vaddr[TD];
 #pragma unroll
-    for (int t = 0; t < TD; ++t)
-        vaddr[t] = unit_v<DH>() * 16 + (4 * g + qq) * (2 * DH) +
-                   (((2 * t + (pp >> 1)) ^ v_swz<DH>(4 * g + qq)) * 16) + (pp & 1) * 8;
+    for (int t = 0; t < TD; ++t) vaddr[t] = v_tr_addr<DH, 2>(g, c, t);
 
     auto dma = [&](int t, auto buf_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
-        const u32x4* sk = srck + (int64_t)t * tile_stride_k;
-        const u32x4* sv = srcv + (int64_t)t * tile_stride_v;
-        lds_c* dk = (lds_c*)(BUF == 0 ? lk0 : lk1) + wv * PW * 1024;
-        lds_c* dv = (lds_c*)(BUF == 0 ? lv0 : lv1) + wv * PWV * 1024;
-#pragma unroll
-        for (int j = 0; j < PW; ++j)
-            __builtin_amdgcn_global_load_lds((const void*)(sk + j * 64),
-                                             (__attribute__((address_space(3))) void*)(dk + j * 1024), 16, 0, 0);
-#pragma unroll
-        for (int j = 0; j < PWV; ++j)
-            __builtin_amdgcn_global_load_lds((const void*)(sv + j * 64),
-                                             (__attribute__((address_space(3))) void*)(dv + j * 1024), 16, 0, 0);
+        dma_pieces<PW>(srck + (int64_t)t * tile_stride_k, (lds_c*)(BUF == 0 ? lk0 : lk1) + wv * PW * 1024);
+        dma_pieces<PWV>(srcv + (int64_t)t * tile_stride_v, (lds_c*)(BUF == 0 ? lv0 : lv1) + wv * PWV * 1024);
     };
-    if (ntile > 0) dma(0, std::integral_constant<int, 0>{});
+    if (ntile > 0) dma(0, B0{});
 
     auto tile = [&](int tt, auto buf_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
-        wait_vm_lgkm0<0>();
-        __builtin_amdgcn_s_barrier();
-        if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
+        tile_enter<BUF>(tt, ntile, dma);
         const int2 ek2 = sck[tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head];
         const int2 ev2 = scv[tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head];
         lds_c* const bk = (lds_c*)(BUF == 0 ? lk0 : lk1);
         lds_c* const bv = (lds_c*)(BUF == 0 ? lv0 : lv1);
-        typedef __attribute__((address_space(3))) u32x4 lds_u4;
-        typedef __attribute__((address_space(3))) s16x4 lds_s4;
         f32x4 sc4[4], dp4[4];
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, b = a;
 #pragma unroll
             for (int kd = 0; kd < KD; ++kd) {
-                const int ko = (((kd * 2 + 0) * 4) * 64 + 16 * n) * 16, lo = (((kd * 2 + 1) * 4) * 64 + 16 * n) * 16;
-                const f16x8 kh = __builtin_bit_cast(f16x8, *(lds_u4*)(bk + kaddr + ko));
-                const f16x8 kl = __builtin_bit_cast(f16x8, *(lds_u4*)(bk + kaddr + lo));
-                const f16x8 vh = __builtin_bit_cast(f16x8, *(lds_u4*)(bv + kaddr + ko));
-                const f16x8 vl = __builtin_bit_cast(f16x8, *(lds_u4*)(bv + kaddr + lo));
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qt[kd][0], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qt[kd][1], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qt[kd][0], a, 0, 0, 0);
-                b = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, dt[kd][0], b, 0, 0, 0);
-                b = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, dt[kd][1], b, 0, 0, 0);
-                b = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, dt[kd][0], b, 0, 0, 0);
+                const f16x8 kh = read_k_frag<f16x8, DH, 2>(bk, kaddr, kd, 0, n);
+                const f16x8 kl = read_k_frag<f16x8, DH, 2>(bk, kaddr, kd, 1, n);
+                const f16x8 vh = read_k_frag<f16x8, DH, 2>(bv, kaddr, kd, 0, n);
+                const f16x8 vl = read_k_frag<f16x8, DH, 2>(bv, kaddr, kd, 1, n);
+                mma_h3(kh, kl, qt[kd][0], qt[kd][1], a);
+                mma_h3(vh, vl, dt[kd][0], dt[kd][1], b);
             }
             sc4[n] = a;
             dp4[n] = b;
@@ -639,18 +531,8 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
 #pragma unroll
             for (int t = 0; t < TD; ++t) {
                 f16x8 vf[2];
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) {
-                    lds_c* const vb = bk + vaddr[t] + tm * (128 * DH) + j * 32 * (2 * DH);
-                    const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)vb);
-                    const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vb + 16 * (2 * DH)));
-                    vf[tm] = __builtin_bit_cast(f16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
-                }
-                f32x4 a = tmp[t];
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[1], pt0, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[0], pt1, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[0], pt0, a, 0, 0, 0);
-                tmp[t] = a;
+                read_v_tr2<DH>(bk + vaddr[t] + j * 32 * (2 * DH), vf);
+                mma_h3(vf[0], vf[1], pt0, pt1, tmp[t]);
             }
         }
         const float fv = __builtin_ldexpf(1.f, -(ek2.y + eds));
@@ -659,14 +541,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[t][r] = __builtin_fmaf(tmp[t][r], fv, acc[t][r]);
     };
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-    int tt = 0;
-    for (; tt + 2 <= ntile; tt += 2) {
-        tile(tt, B0{});
-        tile(tt + 1, B1{});
-    }
-    if (tt < ntile) tile(tt, B0{});
+    tile_loop(ntile, tile);
 
     if (qok) {
 #pragma unroll
@@ -684,7 +559,7 @@ attn_bwd_dq_f16x3_kernel(const float* __restrict__ q, int64_t ld_q, const float*
     // lse2 / D of the block's 64 query rows by query tile for attn_bwd_dkdv_f16x3_kernel (rows
     // past the segment: lse +inf, D 0, so their P and dS vanish there without a mask)
     if (lsed_t && g == 0) {
-        float* t = lsed_t + ((qb / 64 + seg + qblk) * n_head + head) * 128 + wv * 16 + c;
+        float* t = lsed_t + ((seg_tile(qb, seg) + qblk) * n_head + head) * 128 + wv * 16 + c;
         t[0] = qok ? lse2 : INFINITY;
         t[64] = qok ? D : 0.f;
     }
@@ -714,15 +589,12 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
                            int n_head, int n_seg, int n_kv_seg, int n_kblk, float scale,
                            float scale_log2, uint32_t drop_seed, uint32_t drop_thresh, float inv_keep) {
     constexpr int KD = DH / 32, TD = DH / 16;
-    constexpr int UN = units<DH>();
+    constexpr int UN = Img16<DH>::units;
     constexpr int PW = UN / 64 / 4;
     __shared__ u32x4 lq0[UN], lq1[UN], ld0[UN], ld1[UN];
     __shared__ u32x4 ls0[32], ls1[32];                           // [lse2 64 | D 64] per tile
-    typedef __attribute__((address_space(3))) char lds_c;
-    const int L = blockIdx.x, xcd = L & 7, j0 = L >> 3;
-    const int pair = (j0 / n_kblk) * 8 + xcd, kblk = j0 % n_kblk;
-    if (pair >= n_kv_seg * n_head) return;
-    const int ks = pair / n_head, head = pair % n_head;
+    int ks, head, kblk;
+    if (!block_split(n_kblk, n_kv_seg, n_head, ks, head, kblk)) return;
     const int64_t kb = kv_off[ks], ke = kv_off[ks + 1];
     const int64_t k0 = kb + (int64_t)kblk * 64;
     if (k0 >= ke) return;                                        // block-uniform
@@ -769,15 +641,10 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
 #pragma unroll
     for (int t = 0; t < TD; ++t) adk[t] = adv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float one = 1.0f;
-    const uint32_t kaddr = (uint32_t)(g * 64 + c) * 16;
-    const int qq = c >> 2, pp = c & 3;
+    const uint32_t kaddr = k_frag_addr(g, c);
     uint32_t vaddr[TD];
 #pragma unroll
-    for (int t = 0; t < TD; ++t)
-        vaddr[t] = unit_v<DH>() * 16 + (4 * g + qq) * (2 * DH) +
-                   (((2 * t + (pp >> 1)) ^ v_swz<DH>(4 * g + qq)) * 16) + (pp & 1) * 8;
-    typedef __attribute__((address_space(3))) u32x4 lds_u4;
-    typedef __attribute__((address_space(3))) s16x4 lds_s4;
+    for (int t = 0; t < TD; ++t) vaddr[t] = v_tr_addr<DH, 2>(g, c, t);
     typedef __attribute__((address_space(3))) f32x4 lds_v4;
 
     for (int seg = 0; seg < n_seg; ++seg) {
@@ -786,7 +653,7 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
         const int nq = (int)(q_off[seg + 1] - qb);
         const int ntile = (nq + 63) / 64;
         if (ntile == 0) continue;
-        const int64_t tile0 = (qb / 64 + seg) * n_head + head;
+        const int64_t tile0 = seg_tile(qb, seg) * n_head + head;
         const int64_t tstride = (int64_t)n_head * UN;
         const u32x4* srcq = reinterpret_cast<const u32x4*>(imgq) + tile0 * UN + wv * PW * 64 + lane;
         const u32x4* srcd = reinterpret_cast<const u32x4*>(imgd) + tile0 * UN + wv * PW * 64 + lane;
@@ -796,25 +663,19 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
             lds_c* dq_ = (lds_c*)(BUF == 0 ? lq0 : lq1) + wv * PW * 1024;
             lds_c* dd_ = (lds_c*)(BUF == 0 ? ld0 : ld1) + wv * PW * 1024;
 #pragma unroll
-            for (int j = 0; j < PW; ++j) {
-                __builtin_amdgcn_global_load_lds((const void*)(srcq + t * tstride + j * 64),
-                                                 (__attribute__((address_space(3))) void*)(dq_ + j * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const void*)(srcd + t * tstride + j * 64),
-                                                 (__attribute__((address_space(3))) void*)(dd_ + j * 1024), 16, 0, 0);
+            for (int j = 0; j < PW; ++j) {                       // the two images' pieces alternate
+                dma_piece(srcq + t * tstride + j * 64, dq_ + j * 1024);
+                dma_piece(srcd + t * tstride + j * 64, dd_ + j * 1024);
             }
             if (wv == 0 && lane < 32)
-                __builtin_amdgcn_global_load_lds((const void*)(srcl + (int64_t)t * n_head * 32),
-                                                 (__attribute__((address_space(3))) void*)(BUF == 0 ? ls0 : ls1),
-                                                 16, 0, 0);
+                dma_piece(srcl + (int64_t)t * n_head * 32, (lds_c*)(BUF == 0 ? ls0 : ls1));
         };
         __syncthreads();                                         // the previous segment's buffers
         dma(0, std::integral_constant<int, 0>{});
 
         auto tile = [&](int tt, auto buf_tag) {
             constexpr int BUF = decltype(buf_tag)::value;
-            wait_vm_lgkm0<0>();
-            __builtin_amdgcn_s_barrier();
-            if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
+            tile_enter<BUF>(tt, ntile, dma);
             const int64_t ti = tile0 + (int64_t)__builtin_amdgcn_readfirstlane(tt) * n_head;
             const int2 eq2 = scq[ti], ed2 = scd[ti];
             lds_c* const bq = (lds_c*)(BUF == 0 ? lq0 : lq1);
@@ -826,17 +687,12 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
                 f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, b = a;
 #pragma unroll
                 for (int kd = 0; kd < KD; ++kd) {
-                    const int ko = (((kd * 2 + 0) * 4) * 64 + 16 * n) * 16, lo = (((kd * 2 + 1) * 4) * 64 + 16 * n) * 16;
-                    const f16x8 qh = __builtin_bit_cast(f16x8, *(lds_u4*)(bq + kaddr + ko));
-                    const f16x8 ql = __builtin_bit_cast(f16x8, *(lds_u4*)(bq + kaddr + lo));
-                    const f16x8 dh_ = __builtin_bit_cast(f16x8, *(lds_u4*)(bd + kaddr + ko));
-                    const f16x8 dl_ = __builtin_bit_cast(f16x8, *(lds_u4*)(bd + kaddr + lo));
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ql, kt[kd][0], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh, kt[kd][1], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh, kt[kd][0], a, 0, 0, 0);
-                    b = __builtin_amdgcn_mfma_f32_16x16x32_f16(dl_, vt[kd][0], b, 0, 0, 0);
-                    b = __builtin_amdgcn_mfma_f32_16x16x32_f16(dh_, vt[kd][1], b, 0, 0, 0);
-                    b = __builtin_amdgcn_mfma_f32_16x16x32_f16(dh_, vt[kd][0], b, 0, 0, 0);
+                    const f16x8 qh = read_k_frag<f16x8, DH, 2>(bq, kaddr, kd, 0, n);
+                    const f16x8 ql = read_k_frag<f16x8, DH, 2>(bq, kaddr, kd, 1, n);
+                    const f16x8 dh_ = read_k_frag<f16x8, DH, 2>(bd, kaddr, kd, 0, n);
+                    const f16x8 dl_ = read_k_frag<f16x8, DH, 2>(bd, kaddr, kd, 1, n);
+                    mma_h3(qh, ql, kt[kd][0], kt[kd][1], a);
+                    mma_h3(dh_, dl_, vt[kd][0], vt[kd][1], b);
                 }
                 s4[n] = a;
                 d4[n] = b;
@@ -884,25 +740,11 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
 #pragma unroll
                 for (int t = 0; t < TD; ++t) {
                     f16x8 of[2], qf[2];
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm) {
-                        const uint32_t off = vaddr[t] + tm * (128 * DH) + j * 32 * (2 * DH);
-                        const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(bd + off));
-                        const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(bd + off + 16 * (2 * DH)));
-                        of[tm] = __builtin_bit_cast(f16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
-                        const s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(bq + off));
-                        const s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(bq + off + 16 * (2 * DH)));
-                        qf[tm] = __builtin_bit_cast(f16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
-                    }
-                    f32x4 a = tv[t], b = tk[t];
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(of[1], p0, a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(of[0], p1, a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(of[0], p0, a, 0, 0, 0);
-                    b = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[1], s0, b, 0, 0, 0);
-                    b = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[0], s1, b, 0, 0, 0);
-                    b = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[0], s0, b, 0, 0, 0);
-                    tv[t] = a;
-                    tk[t] = b;
+                    const uint32_t off = vaddr[t] + j * 32 * (2 * DH);
+                    read_v_tr2<DH>(bd + off, of);
+                    read_v_tr2<DH>(bq + off, qf);
+                    mma_h3(of[0], of[1], p0, p1, tv[t]);
+                    mma_h3(qf[0], qf[1], s0, s1, tk[t]);
                 }
             }
             const float fv = __builtin_ldexpf(1.f, -(ed2.y + 14));
@@ -943,8 +785,7 @@ attn_bwd_dkdv_f16x3_kernel(const float* __restrict__ k, int64_t ld_k, const floa
 // same tensors, self- or cross-attention). ws: attn_bwd_f16x3_bytes.
 size_t attn_bwd_f16x3_bytes(int64_t n_rows, int32_t n_seg, int32_t n_head, int32_t dh) {
     const int64_t nt = n_tiles16(n_rows, n_seg) * n_head;
-    const int un = dh == 32 ? units<32>() : units<64>();
-    return (size_t)4 * (nt * un * 16 + nt * 8) + (size_t)nt * 128 * 4;
+    return (size_t)4 * kv_space_bytes(nt, dh) + (size_t)nt * 128 * 4;
 }
 
 int attn_bwd_f16x3(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
@@ -957,11 +798,10 @@ int attn_bwd_f16x3(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                    uint32_t drop_thresh, float inv_keep, hipStream_t st) {
     const int32_t nsm = std::max(n_seg, n_kv_seg);
     const int64_t nt = n_tiles16(n_rows, nsm) * nhead;
-    const int un = dh == 32 ? units<32>() : units<64>();
-    const int64_t ib = nt * un * 16 + nt * 8;                      // one image + its exponents
+    const int64_t ib = kv_space_bytes(nt, dh);                     // one image + its exponents
     char* base = static_cast<char*>(ws);
-    auto img = [&](int i) { return reinterpret_cast<uint4*>(base + i * ib); };
-    auto sc = [&](int i) { return reinterpret_cast<int2*>(base + i * ib + nt * un * 16); };
+    auto img = [&](int i) { return kv_space(base + i * ib, nt, dh).img; };
+    auto sc = [&](int i) { return kv_space(base + i * ib, nt, dh).sc; };
     float* lsed = reinterpret_cast<float*>(base + 4 * ib);
     const int n_qblk = (int)ceil_div(max_q_len, 64), n_kblk = (int)ceil_div(max_kv_len, 64);
     const int64_t n_blocks = ceil_div((int64_t)n_seg * nhead, 8) * 8 * n_qblk;
@@ -973,36 +813,19 @@ int attn_bwd_f16x3(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                  {n_kv_seg, n_kv_seg, n_seg, n_seg}, {1, 0, 1, 1}, nsm};
     const dim3 igrid((unsigned)ceil_div(std::max(max_q_len, max_kv_len), 64), (unsigned)nhead,
                      (unsigned)(4 * nsm));
-#define FGR_BWD16(D)                                                                                 \
-    hipLaunchKernelGGL(attn_image16_jobs_kernel<D>, igrid, dim3(256), 0, st, jobs);                   \
-    if (drop)                                                                                        \
-        hipLaunchKernelGGL((attn_bwd_dq_f16x3_kernel<D, true>), dim3((unsigned)n_blocks), dim3(256), 0, st, \
-                           q, ldq, dout, lddo, o, ldo, img(0), sc(0), img(1), sc(1), dq, lddq, q_off,   \
-                           kv_off, kv_seg, nhead, n_seg, n_qblk, scale, sl2, lse_in,                  \
-                           nullptr, dsum_out, lsed, drop_seed,                                        \
-                           drop_thresh, inv_keep);                                                   \
-    else                                                                                             \
-        hipLaunchKernelGGL((attn_bwd_dq_f16x3_kernel<D, false>), dim3((unsigned)n_blocks), dim3(256), 0, st, \
-                           q, ldq, dout, lddo, o, ldo, img(0), sc(0), img(1), sc(1), dq, lddq, q_off,   \
-                           kv_off, kv_seg, nhead, n_seg, n_qblk, scale, sl2, lse_in,                  \
-                           nullptr, dsum_out, lsed, drop_seed,                                        \
-                           drop_thresh, inv_keep);                                                   \
-    if (drop)                                                                                        \
-        hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, true>), dim3((unsigned)n_kblocks), dim3(256), 0, \
-                           st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv,      \
-                           lddv, q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale,       \
-                           sl2, drop_seed, drop_thresh, inv_keep);                                   \
-    else                                                                                             \
-        hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, false>), dim3((unsigned)n_kblocks), dim3(256), 0, \
-                           st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv,      \
-                           lddv, q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale,       \
-                           sl2, drop_seed, drop_thresh, inv_keep);
-    if (dh == 32) {
-        FGR_BWD16(32)
-    } else {
-        FGR_BWD16(64)
-    }
-#undef FGR_BWD16
+    attn_with_modes(dh, drop, [&](auto dh_tag, auto drop_tag) {
+        constexpr int D = decltype(dh_tag)::value;
+        constexpr bool DROP = decltype(drop_tag)::value;
+        hipLaunchKernelGGL(attn_image16_jobs_kernel<D>, igrid, dim3(256), 0, st, jobs);
+        hipLaunchKernelGGL((attn_bwd_dq_f16x3_kernel<D, DROP>), dim3((unsigned)n_blocks), dim3(256), 0, st,
+                           q, ldq, dout, lddo, o, ldo, img(0), sc(0), img(1), sc(1), dq, lddq, q_off,
+                           kv_off, kv_seg, nhead, n_seg, n_qblk, scale, sl2, lse_in, nullptr, dsum_out,
+                           lsed, drop_seed, drop_thresh, inv_keep);
+        hipLaunchKernelGGL((attn_bwd_dkdv_f16x3_kernel<D, DROP>), dim3((unsigned)n_kblocks), dim3(256), 0,
+                           st, k, ldk, v, ldv, img(2), sc(2), img(3), sc(3), lsed, dk, lddk, dv, lddv,
+                           q_off, kv_off, kv_seg, nhead, n_seg, n_kv_seg, n_kblk, scale, sl2, drop_seed,
+                           drop_thresh, inv_keep);
+    });
     FGR_CHECK_LAUNCH("attn_bwd_f16x3");
     return FGR_OK;
 }
@@ -1016,8 +839,7 @@ extern "C" int fgr_attention_f16x3_workspace(int64_t n_kv_rows, int32_t n_kv_seg
     FGR_REQUIRE(bytes && n_kv_rows >= 0 && n_kv_seg >= 0 && n_head > 0,
                 "fgr_attention_f16x3_workspace: bad arguments");
     // sized for the largest supported head dim (64)
-    const int64_t nt = n_tiles16(n_kv_rows, n_kv_seg) * n_head;
-    *bytes = (size_t)(nt * units<64>() * 16 + nt * 8);
+    *bytes = (size_t)kv_space_bytes(n_tiles16(n_kv_rows, n_kv_seg) * n_head, 64);
     return FGR_OK;
 }
 
@@ -1044,46 +866,31 @@ static int attention_f16x3_impl(const float* q, int64_t ld_q, const float* k, in
                   reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
                 "fgr_attention_f16x3: q/k/v/o/workspace must be 16-B aligned");
     const int64_t nt = n_tiles16(n_kv_rows, n_kv_seg) * n_head;
-    const int un = dh == 32 ? units<32>() : units<64>();
-    const int64_t need = nt * un * 16 + nt * 8;
+    const int64_t need = kv_space_bytes(nt, dh);
     FGR_REQUIRE(ws_bytes >= need, "fgr_attention_f16x3: workspace %lld < %lld bytes",
                 (long long)ws_bytes, (long long)need);
     if (max_q_len == 0 || max_kv_len == 0) return FGR_OK;
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
-    uint4* img = static_cast<uint4*>(workspace);
-    int2* sc = reinterpret_cast<int2*>(static_cast<char*>(workspace) + nt * un * 16);
+    const KvSpace kv = kv_space(workspace, nt, dh);
     const dim3 kgrid((unsigned)ceil_div(max_kv_len, 64), (unsigned)n_head, (unsigned)n_kv_seg);
-    if (dh == 32)
-        hipLaunchKernelGGL(attn_kv_image16_kernel<32>, kgrid, dim3(256), 0, st, k, ld_k, v, ld_v,
-                           kv_off, n_head, img, sc);
-    else
-        hipLaunchKernelGGL(attn_kv_image16_kernel<64>, kgrid, dim3(256), 0, st, k, ld_k, v, ld_v,
-                           kv_off, n_head, img, sc);
-    FGR_CHECK_LAUNCH("attn_kv_image16_kernel");
     const int n_qblk = (int)ceil_div(max_q_len, 64);
     const int64_t n_blocks = ceil_div((int64_t)n_seg * n_head, 8) * 8 * n_qblk;
     const float sl2 = scale * 1.4426950408889634f;
-    if (drop_p > 0.f) {
-        const uint32_t thresh = (uint32_t)std::min(4294967295.0, (double)drop_p * 4294967296.0);
-        const float inv_keep = 1.0f / (1.0f - drop_p);
-        if (dh == 32)
-            hipLaunchKernelGGL((attn_f16x3_v2_kernel<32, true>), dim3((unsigned)n_blocks), dim3(256), 0,
-                               st, q, ld_q, (const uint4*)img, (const int2*)sc, o, ld_o, q_off, kv_off,
-                               kv_seg, n_head, n_seg, n_qblk, sl2, 0, drop_seed, thresh, inv_keep, lse_out);
-        else
-            hipLaunchKernelGGL((attn_f16x3_v2_kernel<64, true>), dim3((unsigned)n_blocks), dim3(256), 0,
-                               st, q, ld_q, (const uint4*)img, (const int2*)sc, o, ld_o, q_off, kv_off,
-                               kv_seg, n_head, n_seg, n_qblk, sl2, 0, drop_seed, thresh, inv_keep, lse_out);
-    } else if (dh == 32) {
-        hipLaunchKernelGGL((attn_f16x3_v2_kernel<32>), dim3((unsigned)n_blocks), dim3(256), 0, st, q,
-                           ld_q, (const uint4*)img, (const int2*)sc, o, ld_o, q_off, kv_off, kv_seg,
-                           n_head, n_seg, n_qblk, sl2, 0, 0u, 0u, 1.f, lse_out);
-    } else {
-        hipLaunchKernelGGL((attn_f16x3_v2_kernel<64>), dim3((unsigned)n_blocks), dim3(256), 0, st, q,
-                           ld_q, (const uint4*)img, (const int2*)sc, o, ld_o, q_off, kv_off, kv_seg,
-                           n_head, n_seg, n_qblk, sl2, 0, 0u, 0u, 1.f, lse_out);
-    }
+    const bool drop = drop_p > 0.f;
+    const uint32_t thresh = drop ? (uint32_t)std::min(4294967295.0, (double)drop_p * 4294967296.0) : 0u;
+    const float inv_keep = drop ? 1.0f / (1.0f - drop_p) : 1.f;
+    attn_with_dh(dh, [&](auto dh_tag) {
+        hipLaunchKernelGGL(attn_kv_image16_kernel<decltype(dh_tag)::value>, kgrid, dim3(256), 0, st, k,
+                           ld_k, v, ld_v, kv_off, n_head, kv.img, kv.sc);
+    });
+    FGR_CHECK_LAUNCH("attn_kv_image16_kernel");
+    attn_with_modes(dh, drop, [&](auto dh_tag, auto drop_tag) {
+        hipLaunchKernelGGL((attn_f16x3_v2_kernel<decltype(dh_tag)::value, decltype(drop_tag)::value>),
+                           dim3((unsigned)n_blocks), dim3(256), 0, st, q, ld_q, (const uint4*)kv.img,
+                           (const int2*)kv.sc, o, ld_o, q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 0,
+                           drop ? drop_seed : 0u, thresh, inv_keep, lse_out);
+    });
     FGR_CHECK_LAUNCH("attn_f16x3_v2_kernel");
     return FGR_OK;
 }
@@ -1148,21 +955,15 @@ extern "C" int fgr_attention_f16x3_img(const float* q, int64_t ld_q, const void*
     if (max_q_len == 0 || n_kv_rows == 0) return FGR_OK;
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
-    const int64_t nt = ceil_div(n_kv_rows, 64) * n_head;
-    const int un = head_dim == 32 ? units<32>() : units<64>();
-    const uint4* img = static_cast<const uint4*>(kv_img);
-    const int2* sc = reinterpret_cast<const int2*>(static_cast<const char*>(kv_img) + nt * un * 16);
+    const KvSpaceConst kv = kv_space(kv_img, ceil_div(n_kv_rows, 64) * n_head, head_dim);
     const int n_qblk = (int)ceil_div(max_q_len, 64);
     const int64_t n_blocks = ceil_div((int64_t)n_seg * n_head, 8) * 8 * n_qblk;
     const float sl2 = scale * 1.4426950408889634f;
-    if (head_dim == 32)
-        hipLaunchKernelGGL((attn_f16x3_v2_kernel<32>), dim3((unsigned)n_blocks), dim3(256), 0, st, q, ld_q,
-                           img, sc, o, ld_o, q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 1,
-                           0u, 0u, 1.f);
-    else
-        hipLaunchKernelGGL((attn_f16x3_v2_kernel<64>), dim3((unsigned)n_blocks), dim3(256), 0, st, q, ld_q,
-                           img, sc, o, ld_o, q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 1,
-                           0u, 0u, 1.f);
+    attn_with_dh(head_dim, [&](auto dh_tag) {
+        hipLaunchKernelGGL((attn_f16x3_v2_kernel<decltype(dh_tag)::value, false>),
+                           dim3((unsigned)n_blocks), dim3(256), 0, st, q, ld_q, kv.img, kv.sc, o, ld_o,
+                           q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 1, 0u, 0u, 1.f);
+    });
     FGR_CHECK_LAUNCH("attn_f16x3_v2_kernel (global tiles)");
     return FGR_OK;
 }

@@ -15,12 +15,11 @@
 //   double-buffered LDS image, one barrier per k32 step), swapped orientation (each lane
 //   owns one activation row, 16-B epilogue stores).
 // * fgr_attention_bf16: the flash attention of attention16.hip with single-term bf16 K / V
-//   images ([k-step][g 4][key 64] / [key 64][DH] with the ds_read_b64_tr_b16 swizzle), Q and
+//   images (KvImage<DH, 1>, attn_tile.h), Q and
 //   P rounded to bf16 in registers, head_dim 32 or 64.
 #include <cstring>
-#include <type_traits>
 
-#include "mfma.h"
+#include "attn_tile.h"
 
 namespace fgr {
 namespace {
@@ -53,13 +52,9 @@ struct GemmBfArgs {
     const float* R; int64_t ldr;
     int M, N, K, act, vec_out;
     // K / V attention images (bf16, head dim 64; BM = 64, BN = 128): columns >= kv_col0 go to
-    // the images of their GLOBAL 64-row tile and head (layout of attn_kv_image_bf16_kernel)
+    // the images of their GLOBAL 64-row tile and head (KvImage<64, 1>, attn_tile.h)
     char* kv_img; int n_head; int kv_col0;
 };
-
-// bf16 attention image of head dim 64 (bf_units<64>() below): 1024 16-B units per (tile, head),
-// V from unit 512
-constexpr int bf_units_kv() { return 64 * 8 + 2 * 256; }
 
 template <int BM, int BN, bool KVEC>
 __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
@@ -173,11 +168,12 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
                                          (__bf16)(ok ? acc[j][i][1] + bb.y : 0.f),
                                          (__bf16)(ok ? acc[j][i][2] + bb.z : 0.f),
                                          (__bf16)(ok ? acc[j][i][3] + bb.w : 0.f)};
-                    char* base = p.kv_img + ((int64_t)bm * p.n_head + head) * (int64_t)(bf_units_kv() * 16);
-                    char* dst;
+                    using Img = KvImage<64, 1>;
+                    char* base = p.kv_img + ((int64_t)bm * p.n_head + head) * (int64_t)(Img::units * 16);
+                    char* dst;                             // Img::v_chunk_at / k_unit, spelled out
                     if (isv) {
-                        const int vch = (d0 >> 3) ^ (((key >> 1) & 3) << 1);
-                        dst = base + 512 * 16 + key * 128 + vch * 16 + ((d0 >> 2) & 1) * 8;
+                        const int vch = (d0 >> 3) ^ v_swz<64>(key);
+                        dst = base + Img::unit_v * 16 + key * 128 + vch * 16 + ((d0 >> 2) & 1) * 8;
                     } else {
                         dst = base + (((d0 >> 5) * 4 + ((d0 & 31) >> 3)) * 64 + key) * 16 + ((d0 >> 2) & 1) * 8;
                     }
@@ -217,16 +213,8 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmBfArgs p) {
 }
 
 // ---------------------------------- attention ------------------------------------------
-// 16-B units per (tile, head) image and the first V unit
-template <int DH> constexpr int bf_units() { return DH * 8 + (DH / 32) * 256; }
-template <int DH> constexpr int bf_unit_v() { return (DH / 32) * 256; }
-
-// V image row swizzle (as attention16.hip v_swz): conflict-free transposed reads at DH 32 and 64
-template <int DH>
-__device__ __forceinline__ int bf_v_swz(int key) {
-    if constexpr (DH == 64) return ((key >> 1) & 3) << 1;
-    else return ((key >> 2) & 1) << 1;
-}
+// the single-term images and the tile-loop parts: attn_tile.h
+template <int DH> using ImgBf = KvImage<DH, 1>;
 
 template <int DH>
 __global__ void __launch_bounds__(256)
@@ -238,8 +226,8 @@ attn_kv_image_bf16_kernel(const float* __restrict__ k, int64_t ld_k, const float
     const int64_t kb = kv_off[s];
     const int nk = (int)(kv_off[s + 1] - kb);
     if (tt * 64 >= nk) return;
-    const int64_t tile = (kb / 64 + s + tt) * n_head + h;
-    char* base = reinterpret_cast<char*>(img + tile * bf_units<DH>());
+    const int64_t tile = (seg_tile(kb, s) + tt) * n_head + h;
+    char* base = reinterpret_cast<char*>(img + tile * ImgBf<DH>::units);
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         const int e = threadIdx.x + 256 * i;
@@ -253,11 +241,10 @@ attn_kv_image_bf16_kernel(const float* __restrict__ k, int64_t ld_k, const float
         const __bf16 kt[4] = {(__bf16)kx.x, (__bf16)kx.y, (__bf16)kx.z, (__bf16)kx.w};
         const __bf16 vt[4] = {(__bf16)vx.x, (__bf16)vx.y, (__bf16)vx.z, (__bf16)vx.w};
         const int ks = d0 >> 5, g = (d0 & 31) >> 3, half = (d0 >> 2) & 1;
-        const int vch = (d0 >> 3) ^ bf_v_swz<DH>(key);
-        *reinterpret_cast<uint2*>(base + ((ks * 4 + g) * 64 + key) * 16 + half * 8) =
+        *reinterpret_cast<uint2*>(base + ImgBf<DH>::k_unit(ks, 0, g, key) + half * 8) =
             *reinterpret_cast<const uint2*>(kt);
-        *reinterpret_cast<uint2*>(base + bf_unit_v<DH>() * 16 + key * (2 * DH) + vch * 16 +
-                                  half * 8) = *reinterpret_cast<const uint2*>(vt);
+        *reinterpret_cast<uint2*>(ImgBf<DH>::v_chunk_at(base, 0, key, d0 >> 3) + half * 8) =
+            *reinterpret_cast<const uint2*>(vt);
     }
 }
 
@@ -274,12 +261,11 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
                     const int64_t* __restrict__ kv_off, const int32_t* __restrict__ kv_seg,
                     int n_head, int n_seg, int n_qblk, float scale_log2, int global_tiles) {
     constexpr int KD = DH / 32, TD = DH / 16;
-    constexpr int UN = bf_units<DH>();
+    constexpr int UN = ImgBf<DH>::units;
     constexpr int PW = UN / 64 / 4;
-    // two LDS objects, pointer-addressed (see attn_f16x3_v2_kernel: the next tile's DMA then
+    // two LDS objects, pointer-addressed (see tile_enter, attn_tile.h: the next tile's DMA then
     // does not hold the V reads of the current one)
     __shared__ u32x4 lds_b0[UN], lds_b1[UN];
-    typedef __attribute__((address_space(3))) char lds_c;
     const int L = blockIdx.x, xcd = L & 7, j0 = L >> 3;
     const int pair = (j0 / n_qblk) * 8 + xcd, qblk = j0 % n_qblk;
     if (pair >= n_seg * n_head) return;
@@ -294,7 +280,7 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
     // fgr_gemm_bf16_qkv): the segment's keys then start `lead` rows into its first tile
     const int lead = global_tiles ? (int)(kb & 63) : 0;
     const int ntile = (lead + nk + 63) / 64;
-    const int64_t tile0 = (global_tiles ? kb / 64 : kb / 64 + ks) * n_head + head;
+    const int64_t tile0 = (global_tiles ? global_tile(kb) : seg_tile(kb, ks)) * n_head + head;
     const int64_t tile_stride = (int64_t)n_head * UN;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
@@ -318,48 +304,34 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
 #pragma unroll
     for (int t = 0; t < TD; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
-    const uint32_t kaddr = (uint32_t)(g * 64 + c) * 16;
-    const int qq = c >> 2, pp = c & 3;
+    const uint32_t kaddr = k_frag_addr(g, c);
     uint32_t vaddr[TD];
 #pragma unroll
-    for (int t = 0; t < TD; ++t)
-        vaddr[t] = bf_unit_v<DH>() * 16 + (4 * g + qq) * (2 * DH) +
-                   (((2 * t + (pp >> 1)) ^ bf_v_swz<DH>(4 * g + qq)) * 16) + (pp & 1) * 8;
+    for (int t = 0; t < TD; ++t) vaddr[t] = v_tr_addr<DH, 1>(g, c, t);
     auto dma = [&](int t, auto buf_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
-        const u32x4* src = src_lane + (int64_t)t * tile_stride;
-        __attribute__((address_space(3))) char* dst =
-            (lds_c*)(BUF == 0 ? lds_b0 : lds_b1) + wv * PW * 1024;
-#pragma unroll
-        for (int j = 0; j < PW; ++j)
-            __builtin_amdgcn_global_load_lds((const void*)(src + j * 64),
-                                             (__attribute__((address_space(3))) void*)(dst + j * 1024),
-                                             16, 0, 0);
+        dma_pieces<PW>(src_lane + (int64_t)t * tile_stride,
+                       (lds_c*)(BUF == 0 ? lds_b0 : lds_b1) + wv * PW * 1024);
     };
     // tile tt lives in LDS buffer (tt + shift) & 1 (a masked first tile takes buffer 1)
     const int shift = lead > 0 ? 1 : 0;
     if (ntile > 0) {
-        if (shift) dma(0, std::integral_constant<int, 1>{});
-        else dma(0, std::integral_constant<int, 0>{});
+        if (shift) dma(0, B1{});
+        else dma(0, B0{});
     }
     auto tile = [&](int tt, auto buf_tag, auto mask_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool MASK = decltype(mask_tag)::value;
-        wait_vm_lgkm0<0>();
-        __builtin_amdgcn_s_barrier();
-        if (tt + 1 < ntile) dma(tt + 1, std::integral_constant<int, 1 - BUF>{});
+        tile_enter<BUF>(tt, ntile, dma);
         lds_c* const bp = (lds_c*)(BUF == 0 ? lds_b0 : lds_b1);
-        typedef __attribute__((address_space(3))) u32x4 lds_u4;
-        typedef __attribute__((address_space(3))) s16x4 lds_s4;
         f32x4 s[4];
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kd = 0; kd < KD; ++kd)
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    __builtin_bit_cast(bf16x8, *(lds_u4*)(bp + kaddr + ((kd * 4) * 64 + 16 * n) * 16)),
-                    qt[kd], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(read_k_frag<bf16x8, DH, 1>(bp, kaddr, kd, 0, n),
+                                                            qt[kd], a, 0, 0, 0);
             s[n] = a;
         }
         if constexpr (MASK) {
@@ -403,18 +375,12 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
 #pragma unroll
             for (int e = 0; e < 8; ++e) pt[e] = (__bf16)s[2 * j + (e >> 2)][e & 3];
 #pragma unroll
-            for (int t = 0; t < TD; ++t) {
-                lds_c* const vb = bp + vaddr[t] + j * 32 * (2 * DH);
-                const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)vb);
-                const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vb + 16 * (2 * DH)));
-                const s16x8 w8 = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w8), pt,
-                                                                 acc[t], 0, 0, 0);
-            }
+            for (int t = 0; t < TD; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    __builtin_bit_cast(bf16x8, read_v_tr<DH>(bp + vaddr[t] + j * 32 * (2 * DH))), pt, acc[t],
+                    0, 0, 0);
         }
     };
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
     const int nfull = (lead + nk) / 64;              // tiles [shift, nfull) have 64 valid keys
     int tt = 0;
     if (shift) {                                     // the first tile, keys before the segment masked
@@ -447,7 +413,6 @@ attn_bf16_v2_kernel(const float* __restrict__ q, int64_t ld_q, const uint4* __re
 
 int ksteps_bf(int k) { return (k + 63) / 64 * 2; }     // even: g5 stages read 2 k32-steps
 size_t image_bytes_bf(int n, int k) { return (size_t)((n + 15) / 16) * ksteps_bf(k) * 64 * 16; }
-int64_t n_tiles_bf(int64_t n_kv_rows, int32_t n_kv_seg) { return n_kv_rows / 64 + n_kv_seg + 1; }
 
 }  // namespace
 
@@ -558,7 +523,7 @@ extern "C" int fgr_attention_bf16_workspace(int64_t n_kv_rows, int32_t n_kv_seg,
                                             size_t* bytes) {
     FGR_REQUIRE(bytes && n_kv_rows >= 0 && n_kv_seg >= 0 && n_head > 0,
                 "fgr_attention_bf16_workspace: bad arguments");
-    *bytes = (size_t)(n_tiles_bf(n_kv_rows, n_kv_seg) * n_head * bf_units<64>() * 16);
+    *bytes = (size_t)kv_image_bytes(n_tiles16(n_kv_rows, n_kv_seg) * n_head, 64, 1);
     return FGR_OK;
 }
 
@@ -583,8 +548,7 @@ extern "C" int fgr_attention_bf16(const float* q, int64_t ld_q, const float* k, 
                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o) |
                   reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
                 "fgr_attention_bf16: q/k/v/o/workspace must be 16-B aligned");
-    const int un = dh == 32 ? bf_units<32>() : bf_units<64>();
-    const int64_t need = n_tiles_bf(n_kv_rows, n_kv_seg) * n_head * un * 16;
+    const int64_t need = kv_image_bytes(n_tiles16(n_kv_rows, n_kv_seg) * n_head, dh, 1);
     FGR_REQUIRE(ws_bytes >= need, "fgr_attention_bf16: workspace %lld < %lld bytes",
                 (long long)ws_bytes, (long long)need);
     if (max_q_len == 0 || max_kv_len == 0) return FGR_OK;
@@ -595,19 +559,15 @@ extern "C" int fgr_attention_bf16(const float* q, int64_t ld_q, const float* k, 
     const int n_qblk = (int)ceil_div(max_q_len, 64);
     const unsigned nb = (unsigned)(ceil_div((int64_t)n_seg * n_head, 8) * 8 * n_qblk);
     const float sl2 = scale * 1.4426950408889634f;
-    if (dh == 32) {
-        hipLaunchKernelGGL(attn_kv_image_bf16_kernel<32>, kgrid, dim3(256), 0, st, k, ld_k, v, ld_v,
-                           kv_off, n_head, img);
-        FGR_CHECK_LAUNCH("attn_kv_image_bf16_kernel");
-        hipLaunchKernelGGL(attn_bf16_v2_kernel<32>, dim3(nb), dim3(256), 0, st, q, ld_q,
-                               (const uint4*)img, o, ld_o, q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 0);
-    } else {
-        hipLaunchKernelGGL(attn_kv_image_bf16_kernel<64>, kgrid, dim3(256), 0, st, k, ld_k, v, ld_v,
-                           kv_off, n_head, img);
-        FGR_CHECK_LAUNCH("attn_kv_image_bf16_kernel");
-        hipLaunchKernelGGL(attn_bf16_v2_kernel<64>, dim3(nb), dim3(256), 0, st, q, ld_q,
-                               (const uint4*)img, o, ld_o, q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 0);
-    }
+    attn_with_dh(dh, [&](auto dh_tag) {
+        hipLaunchKernelGGL(attn_kv_image_bf16_kernel<decltype(dh_tag)::value>, kgrid, dim3(256), 0, st, k,
+                           ld_k, v, ld_v, kv_off, n_head, img);
+    });
+    FGR_CHECK_LAUNCH("attn_kv_image_bf16_kernel");
+    attn_with_dh(dh, [&](auto dh_tag) {
+        hipLaunchKernelGGL(attn_bf16_v2_kernel<decltype(dh_tag)::value>, dim3(nb), dim3(256), 0, st, q, ld_q,
+                           (const uint4*)img, o, ld_o, q_off, kv_off, kv_seg, n_head, n_seg, n_qblk, sl2, 0);
+    });
     FGR_CHECK_LAUNCH("attn_bf16_v2_kernel");
     return FGR_OK;
 }
@@ -616,7 +576,7 @@ extern "C" int fgr_attention_bf16(const float* q, int64_t ld_q, const float* k, 
 extern "C" int fgr_kv_image_bf16_bytes(int64_t n_rows, int32_t n_head, int32_t head_dim, size_t* bytes) {
     FGR_REQUIRE(bytes && n_rows >= 0 && n_head > 0 && head_dim == 64,
                 "fgr_kv_image_bf16_bytes: bad arguments (head_dim 64)");
-    *bytes = (size_t)std::max<int64_t>(1, ceil_div(n_rows, 64)) * n_head * bf_units<64>() * 16;
+    *bytes = (size_t)kv_image_bytes(std::max<int64_t>(1, ceil_div(n_rows, 64)) * n_head, 64, 1);
     return FGR_OK;
 }
 

@@ -27,7 +27,7 @@
 // 16-B stores and ds_read_b128 fragment loads); the per-row scale exponents go through a
 // small LDS array. Block ids are remapped so the blocks sharing an A row panel run on one
 // XCD (its L2 keeps the panel). Three kernels, built from one set of parts (chunk_max8,
-// split_a8, rescale_rows, mma_h3, store_out4, store_tile_h3 below; xcd_tile, load_a8 in
+// split_a8, rescale_rows, store_out4, store_tile_h3 below; xcd_tile, load_a8, mma_h3 in
 // mfma.h):
 //   v1  64 x 128, 2 x 2 waves over (n, m), W images flat-copied into LDS too, one k32-step
 //       per stage, one buffer; optionally a staged row-major epilogue
@@ -38,7 +38,7 @@
 // B[k = 8g + e][j = c], C[i = 4g + r][j = c].
 #include <cstring>
 
-#include "mfma.h"
+#include "attn_tile.h"
 
 namespace fgr {
 namespace {
@@ -102,15 +102,6 @@ __device__ __forceinline__ void rescale_rows(f32x4 (&acc)[TN][TM], int (&shr)[TM
             shr[i] = shv;
         }
     }
-}
-
-// the three significant products of a 16x16x32 step (W terms wh + wl, A terms ah + am), the
-// small ones first
-__device__ __forceinline__ void mma_h3(const f16x8& wh, const f16x8& wl, const f16x8& ah,
-                                       const f16x8& am, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, am, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah, acc, 0, 0, 0);
 }
 
 // Stores one lane's 4 consecutive outputs n..n+3 of a row (16-B accesses when vec and the
@@ -1199,13 +1190,13 @@ extern "C" int fgr_corr_head_f16x3(const float* f, int64_t ldf, int32_t m, int32
 }
 
 // ---- the pre-norm in_proj with the attention's K / V images in its epilogue ----------------
-// Image geometry (attention16.hip, head dim 32): one 16 KB image per (global 64-row tile,
-// head), then the int2 scale exponents of all of them.
+// Image geometry (attn_tile.h): one KvImage<DH, 2> per (global 64-row tile, head), then the
+// int2 scale exponents of all of them (kv_space).
 extern "C" int fgr_kv_image_bytes(int64_t n_rows, int32_t n_head, int32_t head_dim, size_t* bytes) {
     FGR_REQUIRE(bytes && n_rows >= 0 && n_head > 0 && (head_dim == 32 || head_dim == 64),
                 "fgr_kv_image_bytes: bad arguments (head_dim 32 or 64)");
     const int64_t nt = std::max<int64_t>(1, ceil_div(n_rows, 64)) * n_head;
-    *bytes = (size_t)(nt * (head_dim == 32 ? 1024 : 2048) * 16 + nt * 8);
+    *bytes = (size_t)kv_space_bytes(nt, head_dim);
     return FGR_OK;
 }
 
@@ -1235,8 +1226,7 @@ extern "C" int fgr_gemm_f16x3_qkv(const float* a, int64_t lda, const void* w_img
     hipStream_t st = as_stream(stream);
     TimedCall timed_(st);
     FGR_REQUIRE(gemm_g5_f16x3_qkv(a, lda, w_img, ksteps_h3(d), wsc, q, ld_q, bias, m, d, n_head,
-                                  static_cast<char*>(kv_img),
-                                  reinterpret_cast<int2*>(static_cast<char*>(kv_img) + nt * 2048 * 16), st),
+                                  static_cast<char*>(kv_img), kv_space(kv_img, nt, 64).sc, st),
                 "fgr_gemm_f16x3_qkv: g5 variant unavailable");
     FGR_CHECK_LAUNCH("gemm_g5_qkv");
     return FGR_OK;
@@ -1275,16 +1265,14 @@ extern "C" int fgr_gemm_f16x3_ln_qkv(const float* x, int64_t ldx, const float* g
     TimedCall timed_(st);
     {
         const WsLn wl{gamma, beta, add, ld_add, eps, gamma2, beta2, out2, ld_out2,
-                      static_cast<char*>(kv_img),
-                      reinterpret_cast<int2*>(static_cast<char*>(kv_img) + nt * 1024 * 16), n_head, d};
+                      static_cast<char*>(kv_img), kv_space(kv_img, nt, 32).sc, n_head, d};
         if (gemm_ws_f16x3(x, ldx, w_img, wsc, q, ld_q, bias, nullptr, 0, m, n, d, FGR_ACT_NONE, st, &wl)) {
             FGR_CHECK_LAUNCH("gemm_ws_ln_qkv");
             return FGR_OK;
         }
     }
     const RsLn ln{gamma, beta, add, ld_add, eps, gamma2, beta2, out2, ld_out2,
-                  static_cast<char*>(kv_img),
-                  reinterpret_cast<int2*>(static_cast<char*>(kv_img) + nt * 1024 * 16), n_head, d};
+                  static_cast<char*>(kv_img), kv_space(kv_img, nt, 32).sc, n_head, d};
     FGR_REQUIRE(gemm_rs_f16x3(x, ldx, w_img, ksteps_h3(d), wsc, q, ld_q, bias, nullptr, 0, m, n, d,
                               FGR_ACT_NONE, st, &ln),
                 "fgr_gemm_f16x3_ln_qkv: row-stationary kernel rejected %d x %d x %d", m, n, d);

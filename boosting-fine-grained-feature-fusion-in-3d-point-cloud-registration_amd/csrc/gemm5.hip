@@ -28,7 +28,7 @@
 // significant products hh, hm, mh in fp32 accumulation).
 // Lane maps of v_mfma_f32_16x16x32_{f16,bf16} (lane l, g = l >> 4, c = l & 15): A[i = c][k =
 // 8g + e], B[k = 8g + e][j = c], C[i = 4g + r][j = c].
-#include "mfma.h"
+#include "attn_tile.h"
 
 namespace fgr {
 namespace {
@@ -50,15 +50,12 @@ struct G5Args {
     int M, N, K, act, vec_out;
     int ksplit; float* part;          // split-K: partials [ksplit][M][N] (scaled, no epilogue)
     // K / V attention images (head dim 64, staged-epilogue 64 x 128 tiles only): columns >=
-    // kv_col0 go to the f16x3 images of their GLOBAL 64-row tile and head (attention16.hip
-    // layout) instead of C; the k | v columns are the last 128 n_head
+    // kv_col0 go to the f16x3 images of their GLOBAL 64-row tile and head (KvImage<64, 2>,
+    // attn_tile.h) instead of C; the k | v columns are the last 128 n_head
     char* kv_img; int2* kv_sc; int n_head; int kv_col0;
 };
 
-// f16x3 attention image geometry for head dim 64 (attention16.hip units<64>, unit_v<64>,
-// v_swz<64>): 2048 16-B units per (tile, head), V from unit 1024
-constexpr int kKv64Units = 2048;
-constexpr int kKv64UnitV = 1024;
+using KvImg64 = KvImage<64, 2>;     // the f16x3 attention images of head dim 64 (attn_tile.h)
 
 // chunk swizzle of A row r (16-B chunk q of a 128-B row line lands at q ^ swz(r)): rows
 // {0-3, 12-15} and {4-11} of one ds_read_b128 lane group hit 16 distinct 16-B bank slots
@@ -487,13 +484,13 @@ __global__ void __launch_bounds__(256 * KW) gemm_g5(G5Args p) {
                             th[j] = (_Float16)x;
                             tl[j] = (_Float16)(x - (float)th[j]);
                         }
-                        char* base = p.kv_img + ti * (int64_t)(kKv64Units * 16);
+                        char* base = p.kv_img + ti * (int64_t)(KvImg64::units * 16);
                         char *d0, *d1;
-                        if (isv) {                          // [term][key][64] f16, chunk ^ v_swz<64>
-                            const int ch = gg ^ (((key >> 1) & 3) << 1);
-                            d0 = base + kKv64UnitV * 16 + key * 128 + ch * 16;
+                        if (isv) {                          // KvImg64::v_chunk_at(base, term, key, gg)
+                            const int ch = gg ^ (((key >> 1) & 3) << 1);   // v_swz<64>(key), spelled out
+                            d0 = base + KvImg64::unit_v * 16 + key * 128 + ch * 16;
                             d1 = d0 + 128 * 64;
-                        } else {                            // [ks][term][g'][key] x 8 dims
+                        } else {                            // KvImg64::k_unit(ks, term, gq, key)
                             const int ks = gg >> 2, gq = gg & 3;
                             d0 = base + (((ks * 2 + 0) * 4 + gq) * 64 + key) * 16;
                             d1 = base + (((ks * 2 + 1) * 4 + gq) * 64 + key) * 16;

@@ -39,7 +39,7 @@
 //
 // K / V attention images (KV; fgr_gemm_f16x3_ln_qkv, head dim 32): the in_proj launch of the
 // pre-norm layer writes the q columns as fp32 and the k / v columns straight into the f16x3
-// attention images that attention16.hip reads (one per GLOBAL 64-row tile and head: the
+// attention images that attention16.hip reads (attn_tile.h; one per GLOBAL 64-row tile and head: the
 // block's 64 rows, RT = 1), instead of fp32 k / v for a separate image launch. A head is two
 // panels: its 8 values per lane stay in registers until both are done, each wave's max |.|
 // goes to LDS, and after the next panel barrier every wave reads the four maxima, takes the
@@ -53,7 +53,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "mfma.h"
+#include "attn_tile.h"
 
 
 namespace fgr {
@@ -114,10 +114,8 @@ constexpr int kRsLookahead = FGR_RS_LA;   // k-steps of W fragments read ahead o
 // LNM: 0 plain, 1 LayerNorm prologue, 2 LayerNorm prologue + row add, 3 as 2 plus a second
 // LayerNorm output of the same rows (the encoder's per-layer output norm), written by the
 // blocks of the first column group
-// f16x3 attention image geometry for head dim 32 (attention16.hip units<32>, unit_v<32>,
-// v_swz<32>): 1024 16-B units per (tile, head), V from unit 512
-constexpr int kKvUnits = 1024;
-constexpr int kKvUnitV = 512;
+// KV: the f16x3 attention images of head dim 32 (attn_tile.h)
+using KvImg32 = KvImage<32, 2>;
 
 template <int RT, int KS, bool RES, int ACT, int LNM, bool HEAD = false, bool KV = false>
 __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
@@ -335,7 +333,7 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
         const float sc = __builtin_ldexpf(1.f, e);
         const int64_t tile = (int64_t)bm * p.n_head + head;
         if (tid == 0) reinterpret_cast<int*>(p.kv_sc + tile)[isv] = e;
-        char* base = p.kv_img + tile * (kKvUnits * 16);
+        char* base = p.kv_img + tile * (KvImg32::units * 16);
         // lane -> (key kl of the wave's 16, 8-dim group gq): one whole 16-B unit per term
         const int kl = lane >> 2, gq = lane & 3;
         const int key = wv * 16 + kl;
@@ -351,9 +349,9 @@ __global__ void __launch_bounds__(256, KV ? 2 : 1) gemm_rs_kernel(RsArgs p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             char* dst;
-            if (isv)                                        // [term][key][32] f16, chunks ^ v_swz
-                dst = base + kKvUnitV * 16 + t * (128 * 32) + key * 64 + (gq ^ (((key >> 2) & 1) << 1)) * 16;
-            else                                            // [term][g'][key] x 8 dims
+            if (isv)                                        // KvImg32::v_chunk_at(base, t, key, gq)
+                dst = base + KvImg32::unit_v * 16 + t * (128 * 32) + key * 64 + (gq ^ v_swz<32>(key)) * 16;
+            else                                            // KvImg32::k_unit(0, t, gq, key)
                 dst = base + ((t * 4 + gq) * 64 + key) * 16;
             *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(tv[t]);
         }

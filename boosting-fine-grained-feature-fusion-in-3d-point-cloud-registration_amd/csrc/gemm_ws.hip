@@ -23,11 +23,11 @@
 // K / V images (KV): each pass of a wave covers two whole heads (32 columns each) of all 64 rows
 // of the block's global 64-row tile, so the tile's power-of-two exponent (max |.| in
 // [2^14, 2^15), as attn_kv_image16_kernel) is a reduction inside the wave; the split terms go
-// to the attention16.hip image layout (K [term][dim group][key], V [term][key][32] with the
-// v_swz chunk swizzle) with 8-B stores (4 dims x fp16 per lane and term).
+// to the image layout of attn_tile.h (KvImage<32, 2>) with 8-B stores (4 dims x fp16 per lane
+// and term).
 //
 // Precision: as gemm_rs.hip (one scale per activation row, three fp16 products per product).
-#include "mfma.h"
+#include "attn_tile.h"
 
 
 namespace fgr {
@@ -40,8 +40,7 @@ constexpr int kWsPanelU = kWsKS * 128;   // 16-B units per W panel of the image
 #endif
 constexpr int kWsRing = FGR_WS_RING;     // register ring of k32 groups (kWsRing - 1 in flight)
 static_assert(kWsRing >= 2 && kWsRing <= 8, "vmcnt holds at most 63");
-constexpr int kKvUnitsWs = 1024;         // attention16.hip units<32>: 16-B units per (tile, head)
-constexpr int kKvUnitVWs = 512;          //   V from unit 512
+using KvImg32 = KvImage<32, 2>;          // the f16x3 attention images of head dim 32 (attn_tile.h)
 
 struct WsArgs {
     const float* A; int64_t lda;
@@ -389,7 +388,7 @@ gemm_ws_kernel(WsArgs p) {
                 const int isv = hd >= p.n_head ? 1 : 0, head = hd - isv * p.n_head;
                 const int64_t tile = (int64_t)t * p.n_head + head;
                 if (lane == 0) reinterpret_cast<int*>(p.kv_sc + tile)[isv] = kv_e[pass][hh];
-                char* base = p.kv_img + tile * (kKvUnitsWs * 16);
+                char* base = p.kv_img + tile * (KvImg32::units * 16);
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     const int key = 16 * rt + c;
@@ -401,10 +400,10 @@ gemm_ws_kernel(WsArgs p) {
 #pragma unroll
                         for (int tt = 0; tt < 2; ++tt) {
                             char* dst;
-                            if (isv)
-                                dst = base + kKvUnitVWs * 16 + tt * (128 * 32) + key * 64 +
-                                      (gq ^ (((key >> 2) & 1) << 1)) * 16 + 8 * (g & 1);
-                            else
+                            if (isv)                // KvImg32::v_chunk_at(base, tt, key, gq)
+                                dst = base + KvImg32::unit_v * 16 + tt * (128 * 32) + key * 64 +
+                                      (gq ^ v_swz<32>(key)) * 16 + 8 * (g & 1);
+                            else                    // KvImg32::k_unit(0, tt, gq, key)
                                 dst = base + ((tt * 4 + gq) * 64 + key) * 16 + 8 * (g & 1);
                             *reinterpret_cast<uint2*>(dst) = tt ? uint2{f[2], f[3]} : uint2{f[0], f[1]};
                         }

@@ -1,5 +1,5 @@
 // Device helpers shared by the matrix-core kernels (gfx950 / CDNA4, wave64): vector types,
-// reductions across the four 16-lane rows, the f16x3 scale exponents, the XCD block order,
+// reductions across the four 16-lane rows, the f16x3 scale exponents and MFMA trio, the XCD block order,
 // the register-staged GEMMs' A unit load, s_waitcnt encodings and the GEMM epilogue of one
 // output. One definition each; all force-inlined.
 #pragma once
@@ -56,6 +56,15 @@ __device__ __forceinline__ int chunk_shift(float cm) {
 }
 // a row's in-flight scale exponent before its first non-zero chunk (its partial sums are 0)
 constexpr int SH_UNSET = 0x3fff;
+
+// ---- the three significant products of an f16x3 16x16x32 step (A-operand terms wh + wl,
+// B-operand terms ah + am), the small ones first
+__device__ __forceinline__ void mma_h3(const f16x8& wh, const f16x8& wl, const f16x8& ah,
+                                       const f16x8& am, f32x4& acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, am, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah, acc, 0, 0, 0);
+}
 
 // ---- XCD-aware block order: hardware dispatches block t to XCD t % 8; the bijective remap
 // of 0..n-1 that gives each XCD a contiguous range of tiles (its L2 keeps what neighbouring

@@ -10,7 +10,7 @@ from .pose import compute_rigid_transform, fast_compute_rigid_transform  # noqa:
 from .regtr import RegTR  # noqa: F401
 from .pipeline import pipeline  # noqa: F401
 from . import refine  # noqa: F401
-from .refine import icp, refine_outputs, score  # noqa: F401
+from .refine import estimate_normals, icp, refine_outputs, score  # noqa: F401
 from . import robust  # noqa: F401
 from .robust import ransac, ransac_outputs  # noqa: F401
 
@@ -35,5 +35,5 @@ def precision():
 
 __all__ = ['RegTR', 'PreprocessorHIP', 'FixedMetaPreprocessor', 'KPFEncoder', 'ops', 'config',
            'fast_compute_rigid_transform', 'compute_rigid_transform', 'build', 'load', 'FgrError',
-           'set_precision', 'precision', 'refine', 'icp', 'score', 'refine_outputs',
+           'set_precision', 'precision', 'refine', 'icp', 'score', 'refine_outputs', 'estimate_normals',
            'robust', 'ransac', 'ransac_outputs']

@@ -200,6 +200,11 @@ SIGNATURES = {
                 _vp, _vp, _vp, _vp, _vp],
     'fgr_registration_score': [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _f32, _vp, _sz,
                                _vp, _vp, _vp, _vp, _vp, _vp],
+    'fgr_estimate_normals_workspace': [_i64, _i32, ctypes.POINTER(_sz)],
+    'fgr_estimate_normals': [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _sz, _vp, _vp, _vp],
+    'fgr_icp_plane_workspace': [_i64, _i64, _i32, ctypes.POINTER(_sz)],
+    'fgr_icp_plane': [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _f32, _i32, _f32, _f32,
+                      _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'fgr_ransac_workspace': [_i64, _i32, _i32, ctypes.POINTER(_sz)],
     'fgr_ransac_pose': [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _i32, ctypes.c_uint32, _i32,
                         _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

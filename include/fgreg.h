@@ -1070,6 +1070,64 @@ int fgr_registration_score(const float* src, const int64_t* src_off, int64_t n_s
                            float max_dist, void* ws, size_t ws_bytes, float* fitness, float* rmse,
                            int32_t* idx, float* d2, double* info, void* stream);
 
+/* ---- surface normals and point-to-plane ICP ----------------------------------------------
+ * fgr_estimate_normals: pts (n_tot, 3) fp32 packed, off (n_clouds + 1) device row offsets,
+ * view (n_clouds, 3) fp32 per-cloud viewpoints or NULL = the origin. The cloud is binned with
+ * the grid of fgr_radius_grid_build at `radius`. For every point p:
+ *   neighbourhood = the points s of p's cloud with ((sx-px)^2 + (sy-py)^2) + (sz-pz)^2 < r2,
+ *     r2 = radius * radius (fp32, strict; p itself is one of them);
+ *   d = s - p in fp32; n = the count, sum d and sum d d^T in fp64 (a product of two fp32 values
+ *     is exact in fp64, only the sums round); C = sum d d^T / n - (sum d / n)(sum d / n)^T;
+ *   n < 3: the normal is (0, 0, 0) and is not counted. Otherwise it is the unit eigenvector of
+ *     C's smallest eigenvalue (fp64 cyclic Jacobi; the lowest index among equal eigenvalues),
+ *     flipped so that normal . (view - p) >= 0 in fp64 and, where that product is exactly 0,
+ *     so that its first non-zero component is positive; stored as fp32.
+ * normals (n_tot, 3) fp32; n_valid (n_clouds) int32 = the points of the cloud with a non-zero
+ * normal. The members of each grid cell are put into ascending row order first, so the sums
+ * are taken in one order: the same bits every run. No floating-point atomics, no readback,
+ * allocation or synchronisation: a call can be captured into a graph. It takes exactly
+ * fgr_estimate_normals_workspace() bytes and refuses a shorter workspace before anything is
+ * launched or written. 4 n_tot + 1024 n_clouds stays below 2^31, n_clouds <= 65535.
+ *
+ * fgr_icp_plane: the arguments, association, fitness, rmse, stopping rule and freezing of
+ * fgr_icp, with tgt_normals (n_tgt_tot, 3) fp32 (of fgr_estimate_normals, or the caller's own
+ * unit normals) and the point-to-plane update. Per pass under T_k, for every source point:
+ *   q = T_k p and its nearest target s exactly as fgr_icp (d2 < max_dist^2 a candidate); a
+ *   candidate whose target has the normal (0, 0, 0) is no inlier (no other target is tried);
+ *   in fp64 from the fp32 q, s, n: rho = n . (q - s), a = [n | q x n] (translation first).
+ * Over the inliers, in fp64 and in fgr_icp's fixed order: n_inl, sum d2, sum rho^2,
+ *   A = sum a a^T (6 x 6), g = sum a rho.
+ *   fitness = n_inl / n_src, rmse = sqrt(sum d2 / n_inl) (the point-to-point distance, so the
+ *   two methods' outputs compare), plane_rmse = sqrt(sum rho^2 / n_inl), all stored as fp32.
+ * The pair is done, in this order of precedence, with status
+ *   0 converged: k >= 1 and |f_k - f_(k-1)| < rel_fitness and |e_k - e_(k-1)| < rel_rmse;
+ *   2 n_inl < 6;
+ *   3 singular: the fp64 Cholesky of A meets a pivot <= 1e-12 trace(A) (one plane, or two
+ *     parallel ones);
+ *   1 k == max_iters.
+ * Otherwise A x = -g, x = (t, w); dR = exp([w]x) by Rodrigues in fp64 (I + [w]x + [w]x^2 / 2
+ * for |w| < 1e-12); T_(k+1) = [dR R_k | dR t_k + t], computed in fp64 from the stored fp32 T_k
+ * and rounded to fp32; n_iters = k + 1. A done pair is frozen at the pose of its last
+ * completed update. status (n_pairs) int32 and info (n_pairs, 6, 6) fp64 are written where
+ * not NULL: info = A of the last pass run, the returned pose's, full and exactly symmetric. It
+ * is the point-to-plane information, not the Redwood gt.info matrix of
+ * fgr_registration_score. max_iters + 1 passes are enqueued whatever the data: no readback,
+ * allocation or synchronisation. It takes exactly fgr_icp_plane_workspace() bytes; the size
+ * limits are fgr_icp's. */
+int fgr_estimate_normals_workspace(int64_t n_tot, int32_t n_clouds, size_t* bytes);
+int fgr_estimate_normals(const float* pts, const int64_t* off, int64_t n_tot, int32_t n_clouds,
+                         float radius, const float* view, void* ws, size_t ws_bytes,
+                         float* normals, int32_t* n_valid, void* stream);
+int fgr_icp_plane_workspace(int64_t n_src_tot, int64_t n_tgt_tot, int32_t n_pairs,
+                            size_t* bytes);
+int fgr_icp_plane(const float* src, const int64_t* src_off, int64_t n_src_tot, const float* tgt,
+                  const int64_t* tgt_off, int64_t n_tgt_tot, const float* tgt_normals,
+                  int32_t n_pairs, int32_t max_src_len, const float* pose_in, float max_dist,
+                  int32_t max_iters, float rel_fitness, float rel_rmse, void* ws,
+                  size_t ws_bytes, float* pose_out, float* fitness, float* rmse,
+                  float* plane_rmse, int32_t* n_iters, int32_t* status, double* info,
+                  void* stream);
+
 /* ---- robust pose: RANSAC over putative correspondences -----------------------------------
  * The estimator between the forward's correspondences and fgr_icp (the reference ships an
  * unreachable one, models/ransaclib; this is not a port of it). a, b are (n_tot, 3) packed

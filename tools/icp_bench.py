@@ -1,9 +1,11 @@
-"""Timing of fgreg.refine (csrc/icp.hip) at the sizes a consumer refines: HIP events around the
-entry points, medians over `reps` calls after a warm-up, one JSON line per workload.
+"""Timing of fgreg.refine (csrc/icp.hip, csrc/normals.hip) at the sizes a consumer refines: HIP
+events around the entry points, medians over `reps` calls after a warm-up, one JSON line per
+workload and method.
 
-  modelnet  8 pairs of 717 + 717 points (fgreg.synthetic.make_batch('modelnet', 8)), r = 0.05
-  3dmatch   one indoor_like_pair of 20k + 20k points, r = 0.05
-  lidar     one lidar_like_pair of 60k + 60k points over 60 m, r = 0.5
+  modelnet  8 pairs of 717 + 717 points (fgreg.synthetic.make_batch('modelnet', 8)), r = 0.05,
+            normals from a 0.1 radius
+  3dmatch   one indoor_like_pair of 20k + 20k points, r = 0.05, normals from a 0.1 radius
+  lidar     one lidar_like_pair of 60k + 60k points over 60 m, r = 0.5, normals from a 1.0 radius
 
 Per workload, from the ground-truth pose perturbed by 2 degrees and 0.4 r:
   score_us      fgr_registration_score: the grid build, one association pass, the finish
@@ -12,14 +14,20 @@ Per workload, from the ground-truth pose perturbed by 2 degrees and 0.4 r:
                 31 association passes and 30 solves
   pass_us       (icp30_us - icp0_us) / 30: one association pass plus one solve
   icp30_default_us  max_iters = 30 with the default tolerances (pairs freeze when they converge)
-  n_iters, fitness, inlier_rmse of that call
+  n_iters, fitness, inlier_rmse of that call (n_iters: the updates to convergence)
+With --method point_to_plane the same figures for fgr_icp_plane, given the target normals
+(estimated once, outside the timed calls), and
+  normals_us    fgr_estimate_normals on the target clouds: the grid build, the cell sort, the
+                eigen-solves
+  n_valid       the targets' valid normals; status of the default call
+score_us, forward_us and host_ms belong to the point_to_point line.
   forward_us    that workload's RegTR forward (random weights, eval), where a config exists
   host_ms       the same loop on the host in fp64 with scipy's cKDTree (workers = 16), the
                 clouds already on the host: context only
 Kernel-level times (association against solve) come from a kernel trace of `--once`.
 
   python tools/icp_bench.py [--reps 50] [--workloads modelnet,3dmatch,lidar] [--no-forward]
-                            [--no-host] [--once]
+                            [--no-host] [--once] [--method both|point_to_point|point_to_plane]
 """
 import argparse
 import json
@@ -56,12 +64,12 @@ def perturbed(gt, r, seed=0):
 def workload(name):
     if name == 'modelnet':
         src, tgt, gt = make_batch('modelnet', 8)
-        return src, tgt, gt, 0.05, 'modelnet'
+        return src, tgt, gt, 0.05, 'modelnet', 0.1
     if name == '3dmatch':
         s, t, p = indoor_like_pair(0, n_points=20000)
-        return [s], [t], p[None], 0.05, '3dmatch'
+        return [s], [t], p[None], 0.05, '3dmatch', 0.1
     s, t, p = lidar_like_pair(0, n_points=60000)
-    return [s], [t], p[None], 0.5, None
+    return [s], [t], p[None], 0.5, None, 1.0
 
 
 def median_us(fn, reps, warmup=5):
@@ -120,38 +128,55 @@ def main():
     ap.add_argument('--workloads', default='modelnet,3dmatch,lidar')
     ap.add_argument('--no-forward', action='store_true')
     ap.add_argument('--no-host', action='store_true')
-    ap.add_argument('--once', action='store_true', help='one fgr_icp call per workload (for a kernel trace)')
+    ap.add_argument('--once', action='store_true', help='one ICP call per workload and method (for a kernel trace)')
+    ap.add_argument('--method', default='both', choices=['both', 'point_to_point', 'point_to_plane'])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('icp_bench needs a GPU')
+    methods = ['point_to_point', 'point_to_plane'] if args.method == 'both' else [args.method]
     for name in args.workloads.split(','):
-        src, tgt, gt, r, cfg_name = workload(name)
+        src, tgt, gt, r, cfg_name, normal_radius = workload(name)
         start = perturbed(gt, r)
         S, Tg = [torch.from_numpy(s).cuda() for s in src], [torch.from_numpy(t).cuda() for t in tgt]
         P = torch.from_numpy(start).cuda()
-        if args.once:
-            fgreg.icp(S, Tg, P, r, rel_fitness=0.0, rel_rmse=0.0)
-            torch.cuda.synchronize()
-            continue
-        res = {'workload': name, 'lib': os.path.basename(_lib.LIB_PATH), 'pairs': len(src),
-               'n_src': int(src[0].shape[0]), 'n_tgt': int(tgt[0].shape[0]), 'r': r, 'reps': args.reps}
-        res['score_us'] = median_us(lambda: fgreg.score(S, Tg, P, r), args.reps)
-        res['icp0_us'] = median_us(lambda: fgreg.icp(S, Tg, P, r, max_iters=0), args.reps)
-        res['icp30_us'] = median_us(lambda: fgreg.icp(S, Tg, P, r, rel_fitness=0.0, rel_rmse=0.0), args.reps)
-        res['pass_us'] = (res['icp30_us'] - res['icp0_us']) / 30
-        res['icp30_default_us'] = median_us(lambda: fgreg.icp(S, Tg, P, r), args.reps)
-        out = fgreg.icp(S, Tg, P, r)
-        res['n_iters'] = out['n_iters'].cpu().tolist()
-        res['fitness'] = [round(v, 4) for v in out['fitness'].cpu().tolist()]
-        res['inlier_rmse'] = [round(v, 5) for v in out['inlier_rmse'].cpu().tolist()]
-        if cfg_name and not args.no_forward:
-            res['forward_us'] = forward_us(cfg_name, src, tgt, max(args.reps // 5, 5))
-        if not args.no_host:
-            t0 = time.perf_counter()
-            iters = [host_icp(s, t, p, r)[1] for s, t, p in zip(src, tgt, start)]
-            res['host_ms'] = (time.perf_counter() - t0) * 1e3
-            res['host_n_iters'] = iters
-        print(json.dumps(res), flush=True)
+        for method in methods:
+            plane = method == 'point_to_plane'
+            kw = {}
+            if plane:
+                est = fgreg.estimate_normals(Tg, normal_radius)
+                kw = {'method': method, 'tgt_normals': est['normals']}
+            icp = lambda **k: fgreg.icp(S, Tg, P, r, **kw, **k)
+            if args.once:
+                icp(rel_fitness=0.0, rel_rmse=0.0)
+                torch.cuda.synchronize()
+                continue
+            res = {'workload': name, 'method': method, 'lib': os.path.basename(_lib.LIB_PATH),
+                   'pairs': len(src), 'n_src': int(src[0].shape[0]), 'n_tgt': int(tgt[0].shape[0]),
+                   'r': r, 'reps': args.reps}
+            if plane:
+                res['normal_radius'] = normal_radius
+                res['normals_us'] = median_us(lambda: fgreg.estimate_normals(Tg, normal_radius), args.reps)
+                res['n_valid'] = est['n_valid'].cpu().tolist()
+            else:
+                res['score_us'] = median_us(lambda: fgreg.score(S, Tg, P, r), args.reps)
+            res['icp0_us'] = median_us(lambda: icp(max_iters=0), args.reps)
+            res['icp30_us'] = median_us(lambda: icp(rel_fitness=0.0, rel_rmse=0.0), args.reps)
+            res['pass_us'] = (res['icp30_us'] - res['icp0_us']) / 30
+            res['icp30_default_us'] = median_us(lambda: icp(), args.reps)
+            out = icp()
+            res['n_iters'] = out['n_iters'].cpu().tolist()
+            res['fitness'] = [round(v, 4) for v in out['fitness'].cpu().tolist()]
+            res['inlier_rmse'] = [round(v, 5) for v in out['inlier_rmse'].cpu().tolist()]
+            if plane:
+                res['status'] = out['status'].cpu().tolist()
+            if cfg_name and not args.no_forward and not plane:
+                res['forward_us'] = forward_us(cfg_name, src, tgt, max(args.reps // 5, 5))
+            if not args.no_host and not plane:
+                t0 = time.perf_counter()
+                iters = [host_icp(s, t, p, r)[1] for s, t, p in zip(src, tgt, start)]
+                res['host_ms'] = (time.perf_counter() - t0) * 1e3
+                res['host_n_iters'] = iters
+            print(json.dumps(res), flush=True)
 
 
 if __name__ == '__main__':

@@ -66,10 +66,14 @@ def wgrad(a: torch.Tensor, b: torch.Tensor, bias_grad=False):
     (and with bias_grad, also the column sums of a: (dW, db)). f16x3 mode:
     fgr_gemm_f16x3_wgrad straight from both activations (widths padded to a multiple of 4),
     db in the same launches; otherwise the GEMM of the transposed copy of a with b as its
-    (transposed) weight image, and fgr_colsum."""
+    (transposed) weight image, and fgr_colsum. rows == 0 gives zeros in both modes."""
     rows, m = a.shape
     n = b.shape[1]
     if lin.MODE != 'f16x3':
+        if rows == 0:                # an empty contraction has no weight image: zeros, as f16x3
+            _dev(a, b)
+            dw = torch.zeros((m, n), dtype=torch.float32, device=a.device)
+            return (dw, torch.zeros((m,), dtype=torch.float32, device=a.device)) if bias_grad else dw
         dw = linear(a.t().contiguous(), b, transpose=True, cache=False)
         return (dw, colsum(a.contiguous())) if bias_grad else dw
     if m % 4 or n % 4:

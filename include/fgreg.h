@@ -1175,6 +1175,78 @@ int fgr_ransac_pose(const float* a, const float* b, const float* w, int64_t n_to
                     int32_t* best_hyp, int32_t* n_updates, uint8_t* inlier_mask, float* hyp_pose,
                     int32_t* hyp_count, void* stream);
 
+/* ---- feature matching: nearest neighbours in descriptor space, then correspondences --------
+ * The second source of correspondences beside the regressed coordinates (the reference ships
+ * the GeoTransformer utilities for it, models/ransaclib/registration_utils.py; this is not a
+ * port of them). Both entry points are one launch on `stream`, whatever the data, without
+ * workspace, atomics, readback, allocation or synchronisation: two runs give the same bits and
+ * a call can be captured into a graph.
+ *
+ * fgr_feature_nn: q (n_q_rows, d) and k (n_k_rows, d) are dense fp32 rows, 16-B aligned;
+ * q_off, kv_off (n_seg + 1 each) and kv_seg (n_seg) are the segment tables of the
+ * cross-attention. Query row r lies in segment s (q_off[s] <= r < q_off[s + 1]); its keys are
+ * the rows kv_off[kv_seg[s]] .. kv_off[kv_seg[s] + 1) of k, numbered j = 0, 1, .. from the
+ * start of that key segment. max_q_len bounds the query segments' lengths.
+ * Score of key j:  s_j = q_r . k_j                  (FGR_MATCH_DOT)
+ *                  s_j = q_r . k_j - |k_j|^2 / 2    (FGR_MATCH_EUCLID: the arg-max of the score
+ *                  is the arg-min of |q_r - k_j|^2; |q_r|^2 never enters a comparison).
+ * Precision: always the fp32-accurate f16x3 split product, whatever the GEMM mode (as
+ *   fgr_pos_mlp_f16x3): every query and key row is scaled by an exact power of two of its own
+ *   (its max |x| into [2^14, 2^15)), split in two fp16 terms, multiplied on the fp16 matrix
+ *   cores with fp32 accumulation, and the fp32 product is unscaled exactly; |k_j|^2 and |q_r|^2
+ *   are fp32 sums over the fp32 rows. Multiplying every row by a power of two therefore changes
+ *   no index and scales best / second exactly.
+ * nn_idx[r]: the arg-max j. On bit-equal scores the LOWEST index wins, in every merge (within
+ *   a lane, across lanes, across key tiles). -1 when the key segment is empty.
+ * best[r], second[r] (second may be NULL): DOT: the best and the second-best score (a
+ *   duplicate of the best counts as second); EUCLID: the squared distances
+ *   max(0, |q_r|^2 - 2 s) of the two. With fewer than two keys second is -inf (DOT) or +inf
+ *   (EUCLID); with none so is best.
+ * FGR_E_ARG, with nothing launched or written: d refused by fgr_feature_nn_supported (1 iff
+ * d % 32 == 0 and 32 <= d <= 512), a metric other than the two, n_seg outside 1..65535, row
+ * counts outside 0..2^31 - 1, max_q_len outside 0..n_q_rows, a NULL table or required operand,
+ * q or k not 16-B aligned. n_q_rows == 0 or max_q_len == 0 returns FGR_OK and touches nothing.
+ * Writes exactly the n_q_rows elements of each output.
+ *
+ * fgr_match_pairs: nn_idx, best, second (n_rows each) are fgr_feature_nn's results on a packed
+ * batch laid out as the forward packs it -- off (2 n_pairs + 1): segments 0 .. n_pairs - 1 are
+ * the source clouds, n_pairs .. 2 n_pairs - 1 the targets, kv_seg[c] = (c + n_pairs) %
+ * (2 n_pairs) -- and xyz (n_rows, 3) the packed coordinates. Pair p owns the output rows
+ * out_off[p] .. out_off[p] + ns + nt (out_off: n_pairs + 1 offsets) of a, b (n_tot, 3) and w
+ * (n_tot), in the row layout of fgreg.robust.correspondences:
+ *   source rows first:  row i       a = src_xyz[i],       b = tgt_xyz[nn(i)]
+ *   then target rows:   row ns + j  a = src_xyz[nn(j)],   b = tgt_xyz[j].
+ * A row without a neighbour (nn = -1 or outside the opposite cloud) gets zeros for the missing
+ * point and w = 0. Weights are 0 / 1:
+ *   FGR_MATCH_SRC        1 on the source rows, 0 on the target rows;
+ *   FGR_MATCH_MUTUAL     1 on source row i iff nn_tgt[nn_src[i]] == i, 0 on every target row
+ *                        (each mutual pair appears once);
+ *   FGR_MATCH_BILATERAL  1 on every row.
+ * With max_ratio > 0 a row also needs best < (max_ratio * max_ratio) * second in fp32 (Lowe's
+ * test on the EUCLID squared distances; best and second are then required). No compaction:
+ * rows that do not take part carry weight 0, which fgr_ransac_pose skips.
+ * n_match[p] = the number of w = 1 rows. With gt_pose ((n_pairs, 3, 4), together with
+ * n_inlier) n_inlier[p] counts the w = 1 rows with d2 < r2, all fp32 without FMA as
+ * fgr_ransac_pose's score: qx = ((R00 x + R01 y) + R02 z) + tx, d = q - b,
+ * d2 = ((dx dx) + dy dy) + dz dz, r2 = inlier_dist * inlier_dist. Counts are integer block
+ * reductions, every element is stored once.
+ * FGR_E_ARG, with nothing launched or written: n_pairs outside 1..65535, an unknown mode,
+ * n_rows outside 0..2^31 - 1, a NULL table, n_match or (n_rows > 0) operand, max_ratio > 0
+ * without best / second, gt_pose without n_inlier or the reverse, gt_pose with inlier_dist not
+ * finite or <= 0. */
+enum { FGR_MATCH_DOT = 0, FGR_MATCH_EUCLID = 1 };
+enum { FGR_MATCH_SRC = 0, FGR_MATCH_MUTUAL = 1, FGR_MATCH_BILATERAL = 2 };
+int fgr_feature_nn_supported(int32_t d);
+int fgr_feature_nn(const float* q, const float* k, int32_t d, int64_t n_q_rows, int64_t n_k_rows,
+                   const int64_t* q_off, const int64_t* kv_off, const int32_t* kv_seg,
+                   int32_t n_seg, int32_t max_q_len, int32_t metric, int32_t* nn_idx, float* best,
+                   float* second, void* stream);
+int fgr_match_pairs(const int32_t* nn_idx, const float* best, const float* second,
+                    const float* xyz, int64_t n_rows, const int64_t* off, const int64_t* out_off,
+                    int32_t n_pairs, int32_t mode, float max_ratio, const float* gt_pose,
+                    float inlier_dist, float* a, float* b, float* w, int32_t* n_match,
+                    int32_t* n_inlier, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ from .pipeline import pipeline  # noqa: F401
 from . import refine  # noqa: F401
 from .refine import estimate_normals, icp, refine_outputs, score  # noqa: F401
 from . import robust  # noqa: F401
-from .robust import ransac, ransac_outputs  # noqa: F401
+from .robust import compat, compat_outputs, ransac, ransac_outputs  # noqa: F401
 from . import match  # noqa: F401
 from .match import feature_match_recall, match_features, match_outputs, register_features  # noqa: F401
 
@@ -38,5 +38,5 @@ def precision():
 __all__ = ['RegTR', 'PreprocessorHIP', 'FixedMetaPreprocessor', 'KPFEncoder', 'ops', 'config',
            'fast_compute_rigid_transform', 'compute_rigid_transform', 'build', 'load', 'FgrError',
            'set_precision', 'precision', 'refine', 'icp', 'score', 'refine_outputs', 'estimate_normals',
-           'robust', 'ransac', 'ransac_outputs', 'match', 'match_features', 'match_outputs',
+           'robust', 'ransac', 'ransac_outputs', 'compat', 'compat_outputs', 'match', 'match_features', 'match_outputs',
            'register_features', 'feature_match_recall']

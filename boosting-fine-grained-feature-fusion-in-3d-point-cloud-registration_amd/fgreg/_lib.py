@@ -208,6 +208,9 @@ SIGNATURES = {
     'fgr_ransac_workspace': [_i64, _i32, _i32, ctypes.POINTER(_sz)],
     'fgr_ransac_pose': [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _i32, ctypes.c_uint32, _i32,
                         _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'fgr_compat_workspace': [_i64, _i32, _i32, _i32, ctypes.POINTER(_sz)],
+    'fgr_compat_pose': [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _f32, _f32, _f32, _i32, _i32, _i32,
+                        _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'fgr_feature_nn_supported': [_i32],
     'fgr_feature_nn': [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
                        _vp],

@@ -184,17 +184,28 @@ def match_outputs(outputs, model=None, layer=-1, features='cond', **kw):
 
 
 def register_features(outputs, inlier_dist, model=None, layer=-1, features='cond', n_hyp=4096,
-                      seed=0, n_refits=4, mask=False, **kw):
+                      seed=0, n_refits=4, mask=False, estimator='ransac', compat_dist=None,
+                      n_seeds=64, k=16, **kw):
     """``match_outputs``, then ``fgreg.ransac`` on its rows and weights -> RANSAC's dict plus
     the match dict under ``'matches'``. ``n_hyp``, ``seed``, ``n_refits`` and ``mask`` go to
     ``ransac``, every other keyword to ``match_outputs`` (a ground-truth ``pose`` is scored at
-    ``inlier_dist`` unless another is given). The returned ``pose`` starts ``fgreg.icp``."""
-    from .robust import ransac
+    ``inlier_dist`` unless another is given). The returned ``pose`` starts ``fgreg.icp``.
+    ``estimator='compat'`` estimates with ``fgreg.compat`` instead, for matches with few
+    inliers: ``compat_dist`` (default ``inlier_dist``), ``n_seeds`` and ``k`` go to it, ``n_hyp``
+    and ``seed`` are ignored, and the dict carries ``best_seed`` in the place of ``best_hyp``."""
+    from .robust import compat, ransac
+    if estimator not in ('ransac', 'compat'):
+        raise _lib.FgrError(f"estimator {estimator!r}: expected 'ransac' or 'compat'")
     if kw.get('pose') is not None:
         kw.setdefault('inlier_dist', inlier_dist)
     m = match_outputs(outputs, model=model, layer=layer, features=features, **kw)
-    out = ransac(m['a'], m['b'], m['w'], inlier_dist=inlier_dist, n_hyp=n_hyp, seed=seed,
-                 n_refits=n_refits, mask=mask)
+    if estimator == 'compat':
+        out = compat(m['a'], m['b'], m['w'], inlier_dist=inlier_dist, n_seeds=n_seeds, k=k,
+                     compat_dist=inlier_dist if compat_dist is None else compat_dist,
+                     n_refits=n_refits, mask=mask)
+    else:
+        out = ransac(m['a'], m['b'], m['w'], inlier_dist=inlier_dist, n_hyp=n_hyp, seed=seed,
+                     n_refits=n_refits, mask=mask)
     out['matches'] = m
     return out
 

@@ -18,6 +18,11 @@ device, and every returned tensor is a device tensor. The draws are a counter-ba
 
 A call can be captured into a graph after one eager call with the same lengths (the row
 offsets of a list of lengths are uploaded once and kept).
+
+``compat`` / ``compat_outputs`` are the estimator for few inliers (csrc/compat.hip behind
+``fgr_compat_pose``, restated in tests/_compat_ref.py): at 3-5 % a uniform 3-point sample is
+almost never all-inlier, so the seeds come from the spatial compatibility of the rows instead,
+without a draw; scoring, selection and refits are RANSAC's, under the same terms as above.
 """
 import torch
 
@@ -52,6 +57,27 @@ def _packed(xs):
     return xs[0].contiguous() if len(xs) == 1 else torch.cat(xs, 0)
 
 
+def _inputs(a, b, weights):
+    """The checked, packed inputs of both estimators -> (a, b, w or None, lengths, offsets)."""
+    A, Bs = _rows(a, 3, 'a'), _rows(b, 3, 'b')
+    W = None if weights is None else _rows(weights, 1, 'weights')
+    lengths = [int(t.shape[0]) for t in A]
+    if [int(t.shape[0]) for t in Bs] != lengths or \
+            (W is not None and [int(t.shape[0]) for t in W] != lengths) or not lengths:
+        raise _lib.FgrError('a, b and weights need the same number of pairs and rows per pair')
+    pa = _packed(A)
+    return pa, _packed(Bs), None if W is None else _packed(W), lengths, _offsets(lengths, pa.device)
+
+
+def _outputs(n_pairs, n_tot, dev, mask):
+    """The outputs both estimators share -> (pose, rmse, n_inliers, n_eligible, best, n_updates,
+    mask bytes or None)."""
+    i32 = lambda: torch.empty(n_pairs, dtype=torch.int32, device=dev)
+    return (torch.empty(n_pairs, 3, 4, dtype=torch.float32, device=dev),
+            torch.empty(n_pairs, dtype=torch.float32, device=dev), i32(), i32(), i32(), i32(),
+            torch.empty(n_tot, dtype=torch.uint8, device=dev) if mask else None)
+
+
 def ransac(a, b, weights=None, *, inlier_dist, n_hyp=4096, w_min=0.0, seed=0, n_refits=4,
            mask=False, hypotheses=False):
     """RANSAC over the correspondences ``a[i] -> b[i]`` (b ~ R a + t) of every pair.
@@ -68,24 +94,13 @@ def ransac(a, b, weights=None, *, inlier_dist, n_hyp=4096, w_min=0.0, seed=0, n_
     tensors ``mask`` (the inliers of the returned pose, in the caller's row order); with
     ``hypotheses`` every hypothesis's ``hyp_pose`` (B, n_hyp, 3, 4) and ``hyp_count``
     (B, n_hyp) int32 (-1: a repeated sample)."""
-    A, Bs = _rows(a, 3, 'a'), _rows(b, 3, 'b')
-    W = None if weights is None else _rows(weights, 1, 'weights')
-    lengths = [int(t.shape[0]) for t in A]
-    if [int(t.shape[0]) for t in Bs] != lengths or \
-            (W is not None and [int(t.shape[0]) for t in W] != lengths) or not lengths:
-        raise _lib.FgrError('a, b and weights need the same number of pairs and rows per pair')
-    pa, pb = _packed(A), _packed(Bs)
-    pw = None if W is None else _packed(W)
+    pa, pb, pw, lengths, off = _inputs(a, b, weights)
     dev = pa.device
     n_tot, n_pairs = int(pa.shape[0]), len(lengths)
-    off = _offsets(lengths, dev)
     nb = _lib.ws_size('fgr_ransac_workspace', n_tot, n_pairs, int(n_hyp))
     ws = ops.scratch(dev, nb)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    pose = torch.empty(n_pairs, 3, 4, dtype=torch.float32, device=dev)
-    rmse = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    n_inl, n_el, best, upd = i32(n_pairs), i32(n_pairs), i32(n_pairs), i32(n_pairs)
-    msk = torch.empty(n_tot, dtype=torch.uint8, device=dev) if mask else None
+    pose, rmse, n_inl, n_el, best, upd, msk = _outputs(n_pairs, n_tot, dev, mask)
     hp = torch.empty(n_pairs, int(n_hyp), 3, 4, dtype=torch.float32, device=dev) if hypotheses else None
     hc = i32(n_pairs, int(n_hyp)) if hypotheses else None
     _lib.check(_lib.load().fgr_ransac_pose(
@@ -99,6 +114,49 @@ def ransac(a, b, weights=None, *, inlier_dist, n_hyp=4096, w_min=0.0, seed=0, n_
         out['mask'] = list(torch.split(msk.bool(), lengths))
     if hypotheses:
         out['hyp_pose'], out['hyp_count'] = hp, hc
+    return out
+
+
+def compat(a, b, weights=None, *, compat_dist, inlier_dist, n_seeds=64, k=16, w_min=0.0,
+           n_refits=4, mask=False, seeds=False, scores=False):
+    """Pose from spatial compatibility, for correspondences with few inliers (csrc/compat.hip
+    behind ``fgr_compat_pose``; include/fgreg.h states the semantics, tests/_compat_ref.py
+    restates them). Inputs, eligibility and refits as ``ransac``; no draws: rows i, j are
+    compatible when the lengths |a_i - a_j| and |b_i - b_j| differ by less than
+    ``compat_dist``, a row's score sums the common compatible rows over its compatible rows,
+    the ``n_seeds`` best-scored rows each solve a pose from their ``k - 1`` most compatible
+    neighbours, and the pose with the most rows within ``inlier_dist`` is refitted.
+
+    Returns ``ransac``'s dict with ``best_seed`` (the winning seed's position, -1: no valid
+    seed) in the place of ``best_hyp``; with ``seeds`` also ``seed_row`` (B, n_seeds) int32 (the
+    seed's row within its pair, -1: unused), ``seed_pose`` (B, n_seeds, 3, 4) and ``seed_count``
+    (B, n_seeds) int32 (-1: invalid); with ``scores`` a per-pair list ``row_score`` (int32, -1
+    on rows that do not take part)."""
+    pa, pb, pw, lengths, off = _inputs(a, b, weights)
+    dev = pa.device
+    n_tot, n_pairs, max_len, ns = int(pa.shape[0]), len(lengths), max(lengths), int(n_seeds)
+    nb = _lib.ws_size('fgr_compat_workspace', n_tot, n_pairs, max_len, ns)
+    ws = ops.scratch(dev, nb)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    pose, rmse, n_inl, n_el, best, upd, msk = _outputs(n_pairs, n_tot, dev, mask)
+    rs = i32(n_tot) if scores else None
+    sr = i32(n_pairs, ns) if seeds else None
+    sp = torch.empty(n_pairs, ns, 3, 4, dtype=torch.float32, device=dev) if seeds else None
+    sc = i32(n_pairs, ns) if seeds else None
+    _lib.check(_lib.load().fgr_compat_pose(
+        ops._ptr(pa), ops._ptr(pb), ops._ptr(pw), n_tot, ops._ptr(off), n_pairs, max_len,
+        float(w_min), float(compat_dist), float(inlier_dist), ns, int(k), int(n_refits),
+        ops._ptr(ws), nb, ops._ptr(pose), ops._ptr(n_inl), ops._ptr(rmse), ops._ptr(n_el),
+        ops._ptr(best), ops._ptr(upd), ops._ptr(msk), ops._ptr(rs), ops._ptr(sr), ops._ptr(sp),
+        ops._ptr(sc), ops._stream()), 'fgr_compat_pose')
+    out = {'pose': pose, 'n_inliers': n_inl, 'n_eligible': n_el, 'inlier_rmse': rmse,
+           'best_seed': best, 'n_updates': upd}
+    if mask:
+        out['mask'] = list(torch.split(msk.bool(), lengths))
+    if seeds:
+        out['seed_row'], out['seed_pose'], out['seed_count'] = sr, sp, sc
+    if scores:
+        out['row_score'] = list(torch.split(rs, lengths))
     return out
 
 
@@ -121,3 +179,10 @@ def ransac_outputs(outputs, inlier_dist, layer=-1, **kw):
     weights); keyword arguments as ``ransac``. The returned ``pose`` starts ``fgreg.icp``."""
     a, b, w = correspondences(outputs, layer)
     return ransac(a, b, w, inlier_dist=inlier_dist, **kw)
+
+
+def compat_outputs(outputs, compat_dist, inlier_dist, layer=-1, **kw):
+    """``compat`` on the forward's correspondences of decoder layer ``layer``, as
+    ``ransac_outputs``; keyword arguments as ``compat``."""
+    a, b, w = correspondences(outputs, layer)
+    return compat(a, b, w, compat_dist=compat_dist, inlier_dist=inlier_dist, **kw)

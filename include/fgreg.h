@@ -1175,6 +1175,64 @@ int fgr_ransac_pose(const float* a, const float* b, const float* w, int64_t n_to
                     int32_t* best_hyp, int32_t* n_updates, uint8_t* inlier_mask, float* hyp_pose,
                     int32_t* hyp_count, void* stream);
 
+/* ---- robust pose: seeds from spatial compatibility ----------------------------------------
+ * The estimator for few inliers (3-5 %: descriptor matches of low-overlap pairs), where a
+ * uniform 3-point sample is all-inlier with probability p^3 and fgr_ransac_pose would need
+ * hundreds of thousands of hypotheses. Two correct correspondences preserve the distance
+ * between their points, so the inliers form a dense clique of the compatibility graph, and a
+ * seed from it yields an all-inlier sample without a draw (the first- and second-order measure
+ * of SC2-PCR, reduced to its integer core). a, b, w, off and the eligibility are
+ * fgr_ransac_pose's: row i is eligible iff w == NULL or w[i] > w_min, m = n_eligible[p], the
+ * eligible rows keep their order and a rank is a position in that order. max_len is the
+ * caller's bound on a pair's row count; it sizes the workspace and the launches. A pair with
+ * more than max_len eligible rows gets no seed (best_seed = -1, row_score = -1).
+ *
+ * First order, for ranks i != j, all fp32 without FMA:
+ *   dx = ax_i - ax_j (dy, dz likewise), l2 = ((dx dx) + dy dy) + dz dz, la = sqrt(l2)
+ *   correctly rounded; lb the same from b; SC_ij = |la - lb| < compat_dist (a NaN makes it 0),
+ *   SC_ii = 0. Symmetric by construction ((x - y)^2 == (y - x)^2 exactly). Stored as bits, one
+ *   row per rank in 64-bit words; bits past m are 0.
+ * Second order: c_ij = popcount(row_i & row_j), s_i = sum_j SC_ij c_ij in int32 (<= m^2).
+ *   row_score (n_tot, may be NULL), in the caller's row order: s_i, and -1 on ineligible rows.
+ * Seeds: the min(n_seeds, m) ranks with the largest s, ties to the lowest rank, in that order:
+ *   seed position q = 0, 1, .. seed_row (n_pairs, n_seeds; may be NULL): the seed's row index
+ *   within its pair in the caller's numbering, -1 in unused positions.
+ * Consensus set of seed i: i and the at most k - 1 ranks j with SC_ij = 1 and the largest c_ij,
+ *   ties to the lowest j. Fewer than 3 members (or an unused position) make the seed invalid:
+ *   seed_count = -1, seed_pose = identity, it never wins.
+ * Solve: the unweighted fp64 Kabsch over the members with the moments of fgr_ransac_pose's
+ *   refit -- n, sum a, sum b, sum a b^T, H = sum a b^T - (sum a)(sum b)^T / n, summed in a
+ *   fixed order without floating-point atomics -- R = V U^T of H's SVD with the reflection fix,
+ *   t = bm - R am, rounded once to an fp32 (3, 4) pose.
+ * Score, selection, refits and outputs are fgr_ransac_pose's with the seed position in the
+ *   place of h: the count of eligible rows with d2 < r2 (fp32 without FMA, r2 = inlier_dist *
+ *   inlier_dist); the largest count wins, ties go to the earliest position -> best_seed;
+ *   without a valid seed best_seed = -1, pose = identity, n_inliers = 0, inlier_rmse = 0,
+ *   n_updates = 0, mask all 0; at most n_refits refits with the same adopt / stop rules; pose,
+ *   n_inliers, inlier_rmse, n_eligible, n_updates, inlier_mask as there. Each where not NULL:
+ *   seed_pose (n_pairs, n_seeds, 3, 4) and seed_count (n_pairs, n_seeds), every position's
+ *   pose and score.
+ * FGR_E_ARG, with nothing launched or written: n_pairs outside 1..65535, n_tot outside
+ * 0..2^31 - 1, max_len outside 0..8192, n_seeds outside 1..1024, k outside 3..256,
+ * n_refits < 0, compat_dist or inlier_dist not finite or <= 0, a NULL required pointer (a, b
+ * may be NULL when n_tot == 0), ws not 16-B aligned, ws_bytes below fgr_compat_workspace() (a
+ * function of (n_tot, n_pairs, max_len, n_seeds) only: the compacted rows, their row indices
+ * and scores, n_tot rows of bits at max_len's stride, one rank and one 64-B slot per seed;
+ * exactly the bytes used). Six launches on `stream`, whatever the data: no readback,
+ * allocation, synchronisation or floating-point atomic (s_i is summed by integer atomics,
+ * which no order changes), so two runs give the same bits and a call can be captured into a
+ * graph. */
+int fgr_compat_workspace(int64_t n_tot, int32_t n_pairs, int32_t max_len, int32_t n_seeds,
+                         size_t* bytes);
+int fgr_compat_pose(const float* a, const float* b, const float* w, int64_t n_tot,
+                    const int64_t* off, int32_t n_pairs, int32_t max_len, float w_min,
+                    float compat_dist, float inlier_dist, int32_t n_seeds, int32_t k,
+                    int32_t n_refits, void* ws, size_t ws_bytes, float* pose,
+                    int32_t* n_inliers, float* inlier_rmse, int32_t* n_eligible,
+                    int32_t* best_seed, int32_t* n_updates, uint8_t* inlier_mask,
+                    int32_t* row_score, int32_t* seed_row, float* seed_pose, int32_t* seed_count,
+                    void* stream);
+
 /* ---- feature matching: nearest neighbours in descriptor space, then correspondences --------
  * The second source of correspondences beside the regressed coordinates (the reference ships
  * the GeoTransformer utilities for it, models/ransaclib/registration_utils.py; this is not a
